@@ -9,8 +9,12 @@ A step = one density evaluation of one batch resident in HBM, through the drop-i
 followed, when N > 1, by one RCCL all-reduce of (sum, count).  Every rank holds its own 2^20
 rows (weak scaling); value = rows of all ranks / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c3|c2t|c3t|...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c4|c3|c2t|c3t|...] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what the headline does not need:
+the CPU baseline and parity check, the forward (sampling) direction and, on the default c2 line, the other
+configurations as `secondary`.  --dump-outputs DIR writes what the timed path returned in its last step as .npy files.
 """
 from __future__ import annotations
 
@@ -59,6 +63,29 @@ WORKLOADS = {
                          "Adam (SURVEY 8f rank 1 for BASELINE configs[2]'s model; tests/test_flows.py:89-99 trains it)"),
 }
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md chip table
+# --dump-outputs: the workloads whose last timed step is the same from run to run (fixed parameters, seeded input).  The
+# training steps prime for a fixed time, so the parameters their last step sees depend on how many steps ran, and
+# sample_z (c5, c5b) draws fresh masks on every call.
+DUMPABLE = ("c2", "c4", "c3", "c6", "c2f", "c3f", "c1")
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write every array as out_dir/<name>.npy in float32 (float64 stays float64).  Each gets an equal share of the
+    64 MB budget; a larger one is replaced by a fixed, seeded sample of its rows (sorted indices, same every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        row_bytes = t.element_size() * max(1, t[0].numel() if t.dim() else 1)
+        if t.dim() and t.numel() * t.element_size() > share:
+            keep = share // row_bytes
+            idx = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def build_c3(device):
@@ -366,7 +393,7 @@ def main_c5(args, rank, world, device, dim, rows, desc, n_out: int = 50) -> None
                                "kernel": "rnvp_mfma_kernel<50,seeded>", "avg_kernel_us": avg_s * 1e6,
                                "algorithmic_flops_per_launch": flops, "launches_timed": len(kern_ms),
                                "algorithmic_GBps": (12 * dim + 8) * rows / avg_s / 1e9}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             from oracle import flow_oracle as O
 
             n = 1 << 17
@@ -424,12 +451,21 @@ def main_c1(args, rank, world, device, dim, rows, desc) -> None:
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / n
 
+    last = [None]
+
+    def eager():
+        last[0] = model.log_prob(x, return_sum=True)
+
     with torch.no_grad():
         t_prime = time.perf_counter()
         while (time.perf_counter() - t_prime) * 1e3 < args.prime_ms:
             model.log_prob(x, return_sum=True)
             torch.cuda.synchronize()
-        eager_s = timed(lambda: model.log_prob(x, return_sum=True), args.steps)
+        eager_s = timed(eager, args.steps)
+        if args.dump_outputs:
+            lp_last, tot_last = last[0]
+            dump_outputs(args.dump_outputs, {"log_prob": lp_last, "log_prob_sum": tot_last})
+        last[0] = None
         _, tot = model.log_prob(x, return_sum=True)
         replay = model.graphed_log_prob(x)
         graph_s = timed(lambda: replay(x), args.steps)
@@ -446,7 +482,7 @@ def main_c1(args, rank, world, device, dim, rows, desc) -> None:
                      "kernel": "(launch-bound: latency reported instead, SURVEY 8d)", "avg_kernel_us": None},
         "mean_log_prob": float(tot) / rows, "mean_log_prob_graphed": float(tot_g) / rows,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import flow_oracle as O
 
         layers = [{"kind": "affine_half", "parity": bool(i % 2), "params": sd}
@@ -537,7 +573,7 @@ def main_train(args, rank, world, device, dim, rows, desc) -> None:
     else:
         out["roofline"] = {"bound": "mfma", "achieved": None, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": None,
                            "traffic": None, "kernel": "ahf_bwd_mfma_kernel<32,24> (MNF_BWD_FP32=1 / MNF_FP32_MFMA=1)"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the oracle's training step on the host: forward through the restated reference path, torch.autograd backward
         # (the parameter update is negligible next to it), on a bounded slice of the same batch
         from oracle import flow_oracle as O
@@ -663,7 +699,7 @@ def main_train_c5(args, rank, world, device, dim, rows, desc) -> None:
                            "launches_timed": len(kern_ms), "launches_per_step": 2,
                            "note": "z and grad_x in, grad_z out; launch A of the same pass reads z twice and grad_x once "
                                    "more (DESIGN.md 3.5)"}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # the oracle's training step on the host (sample_z + MNFLinear.forward restated, torch.autograd backward) on a
         # bounded slice, with the masks and both noise draws materialised so that the GPU leg below sees the same ones
         from oracle import flow_oracle as O
@@ -857,7 +893,7 @@ def main_train_c3(args, rank, world, device, dim, rows, desc) -> None:
     }
     apply_valu_convention(out["roofline"], "c3t", avg_s)
     apply_transcendental_floor(out["roofline"], "c3t", rows, out["ms_per_step"])
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import flow_oracle as O
 
         n = 1 << 13
@@ -1000,9 +1036,21 @@ def main() -> None:
     ap.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default (c2, one GPU) run only: skip the 20-step runs of the other configurations that are "
-                         "attached to the line as `secondary`")
+                    help="default (c2, one GPU) run with --full only: skip the 20-step runs of the other configurations "
+                         "that are attached to the line as `secondary`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: the CPU baseline and the parity "
+                         "check against the CPU oracle, the forward (sampling) direction, and on the default c2 line "
+                         "the other configurations as `secondary`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         f"(float32 / float64, at most 64 MB in all; workloads {', '.join(DUMPABLE)})")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload not in DUMPABLE:
+        ap.error(f"--dump-outputs: --workload {args.workload}'s last step differs from run to run "
+                 f"(supported: {', '.join(DUMPABLE)})")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # No launcher around us: start the N ranks ourselves, as CHILD processes, before this process has
@@ -1075,18 +1123,21 @@ def main() -> None:
     n_layers = len(model.flows)
 
     pending = [None]
+    last = [None]  # (--dump-outputs) the latest pass's (log_prob, sum)
 
     def step():
         """One pass over the batch + the global mean.  world > 1: the 16-byte RCCL all-reduce of this pass is left
         in flight on RCCL's stream and collected at the start of the next pass, so it overlaps the next pass's
         kernel instead of sitting between two passes; finish() collects the last one inside the timed region."""
         lp, total = model.log_prob(x, return_sum=True)
+        if args.dump_outputs:
+            last[0] = (lp, total)
         prev, pending[0] = pending[0], reduce_sum_count(total, rows, async_op=True)
         return prev.result() if prev is not None else None
 
     def finish():
-        last, pending[0] = pending[0], None
-        return last.result()
+        prev, pending[0] = pending[0], None
+        return prev.result() if prev is not None else None
 
     with torch.no_grad():
         # setup: pack parameter images, let the caching allocator reach its steady state and bring
@@ -1151,6 +1202,10 @@ def main() -> None:
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         gc.enable()
+        if args.dump_outputs and rank == 0:
+            lp_last, tot_last = last[0]
+            dump_outputs(args.dump_outputs, {"log_prob": lp_last, "log_prob_sum": tot_last, "mean_log_prob": mean})
+        last[0] = None
         events, model.layer_events = model.layer_events, None
         if events is None:  # experiment mode: time the kernels in a separate pass instead
             model.layer_events = []
@@ -1162,15 +1217,17 @@ def main() -> None:
             events, model.layer_events = model.layer_events, None
         model.layer_event_pick = None
 
-    # the other direction (sampling: z -> x), outside the timed region, for the record
-    with torch.no_grad():
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(max(1, args.steps // 2)):
-            xs_fwd, _ = model.forward(x)
-        torch.cuda.synchronize()
-        fwd_rate = rows * max(1, args.steps // 2) / (time.perf_counter() - t1)
-        del xs_fwd
+    # the other direction (sampling: z -> x), outside the timed region, for the record (--full)
+    fwd_rate = None
+    if args.full:
+        with torch.no_grad():
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(max(1, args.steps // 2)):
+                xs_fwd, _ = model.forward(x)
+            torch.cuda.synchronize()
+            fwd_rate = rows * max(1, args.steps // 2) / (time.perf_counter() - t1)
+            del xs_fwd
 
     elapsed, per_rank_s = rank_times(elapsed, world, device, backend)
     gpu_mean = float(mean.item())
@@ -1256,15 +1313,16 @@ def main() -> None:
                                 n_fused * 2 * 2 * (2 * (dim // 2) * 24 + 2 * 24 * 24)) * rows / avg_kernel_s / 1e12,
             },
             "mean_log_prob": gpu_mean,
-            "forward_direction_samples_per_s_per_gpu": fwd_rate,
         }
+        if fwd_rate is not None:
+            out["forward_direction_samples_per_s_per_gpu"] = fwd_rate
         if args.workload in ("c3", "c3f"):
             # the spline kernel is VALU / transcendental bound by construction (264 B per row against
             # ~2,300 vector instructions per 16 rows per layer): the roofline it is priced against is the vector
             # ISSUE rate; the HBM figures stay in the object under their own names.
             apply_valu_convention(out["roofline"], "c3", avg_kernel_s)
             apply_transcendental_floor(out["roofline"], "c3", rows, out["ms_per_step"])
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             info, cpu_mean, n = cpu_baseline(layers, dim, x)
             with torch.no_grad():
                 _, tot = model.log_prob(x[:n].contiguous(), return_sum=True)
@@ -1273,7 +1331,7 @@ def main() -> None:
             out["parity"] = {"rows": n, "mean_log_prob_gpu": gpu_sample_mean, "mean_log_prob_cpu": cpu_mean,
                              "rel_err": abs(gpu_sample_mean - cpu_mean) / abs(cpu_mean), "tolerance": 1e-5}
             out["speedup_vs_cpu"] = out["value"] / info["value"]
-        if world == 1 and args.workload == "c2" and not args.no_secondary:
+        if world == 1 and args.workload == "c2" and args.full and not args.no_secondary:
             out["secondary"] = secondary_lines(args)
         print(json.dumps(out))
     if world > 1:

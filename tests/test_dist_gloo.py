@@ -102,6 +102,23 @@ def test_bench_spawns_its_ranks_as_child_processes():
     assert out.stderr.count("needs an MI355X") >= 1 and "local_rank" in out.stderr, out.stderr[-1500:]
 
 
+def test_bench_refuses_to_dump_a_last_step_that_differs_from_run_to_run(tmp_path):
+    """--dump-outputs is for comparing two builds output for output: a workload whose last timed step depends on how
+    many steps ran before it (the training steps prime for a fixed time) is refused at the command line, before any
+    GPU work, and nothing is written."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "c2t", "--dump-outputs",
+                          str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 2 and "--dump-outputs" in out.stderr, out.stderr[-1500:]
+    assert not (tmp_path / "out").exists()
+    usage = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True,
+                           timeout=300)
+    assert usage.returncode == 0 and "--full" in usage.stdout and "--dump-outputs" in usage.stdout
+
+
 def _actnorm_worker(rank, world, port, rows, dim, out):
     import sys
 

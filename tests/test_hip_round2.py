@@ -121,10 +121,29 @@ def test_bench_single_gpu_line(amd):
     assert "secondary" not in line
 
 
+def test_bench_plain_line_is_lean_and_dumps_its_last_step(amd, tmp_path):
+    """A plain run times exactly --steps steps and carries none of --full's extras; --dump-outputs writes what the last
+    timed step returned (log-prob per row, its sum, the global mean), and two runs with the same arguments agree."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    lines = [run_bench("--steps", "4", "--warmup", "0", "--prime-ms", "5", "--dump-outputs", str(d)) for d in dirs]
+    for line in lines:
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and len(line["distributed"]["ms_per_step_per_rank"]) == 1
+        assert not {"cpu_baseline", "parity", "secondary", "forward_direction_samples_per_s_per_gpu"} & set(line)
+    a, b = ({n: np.load(d / f"{n}.npy") for n in ("log_prob", "log_prob_sum", "mean_log_prob")} for d in dirs)
+    rows = lines[0]["config"]["rows_per_gpu"]
+    assert a["log_prob"].shape == (rows,) and a["log_prob"].dtype == np.float32
+    assert a["log_prob_sum"].dtype == np.float64 and a["mean_log_prob"].dtype == np.float64
+    assert float(a["mean_log_prob"]) == lines[0]["mean_log_prob"]
+    np.testing.assert_allclose(a["log_prob"].astype(np.float64).sum(), a["log_prob_sum"][0], rtol=1e-6)
+    np.testing.assert_allclose(float(a["log_prob_sum"][0]) / rows, float(a["mean_log_prob"]), rtol=1e-12)
+    np.testing.assert_allclose(a["log_prob"], b["log_prob"], rtol=1e-6, atol=0)
+    assert sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) <= 64 << 20
+
+
 def test_bench_training_step_line(amd):
     """--workload c2t: one Adam step of the C2 model per step; the line carries the gradient kernel's roofline, the
     oracle's training step on the host as cpu_baseline and the gradients' parity against the float64 oracle."""
-    line = run_bench("--workload", "c2t", "--steps", "3", "--warmup", "1", "--prime-ms", "5")
+    line = run_bench("--workload", "c2t", "--steps", "3", "--warmup", "1", "--prime-ms", "5", "--full")
     r = line["roofline"]
     assert line["unit"] == "samples/s" and r["bound"] == "hbm" and "ahf_bwd_split_kernel" in r["kernel"]
     assert r["launches_timed"] == 3 * 9 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
@@ -137,7 +156,7 @@ def test_bench_training_step_line(amd):
 def test_bench_c3_training_step_line(amd):
     """--workload c3t: one Adam step of config 3's model per step; the NSF_CL row gradient kernel's roofline figures,
     the oracle's training step as cpu_baseline, the gradients' parity against the float64 oracle."""
-    line = run_bench("--workload", "c3t", "--steps", "3", "--warmup", "1", "--prime-ms", "5")
+    line = run_bench("--workload", "c3t", "--steps", "3", "--warmup", "1", "--prime-ms", "5", "--full")
     r = line["roofline"]
     assert line["unit"] == "samples/s" and "nsf_bwd_tile_kernel" in r["kernel"] and r["bound"] == "valu"
     assert r["launches_timed"] == 3 * 3 and abs(r.get("frac_plain_count", r["frac"]) - r["achieved"] / r["peak"]) < 1e-12

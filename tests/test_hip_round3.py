@@ -505,7 +505,7 @@ def test_bench_c5t_training_step_line(amd):
     """--workload c5t: one Adam step of MNFLinear(800, 50) at 256,000 rows per step; the line carries launch B-ts's
     roofline, the oracle's training step as cpu_baseline and the gradients' parity against the float64 oracle at
     1e-5 + twice the fp32 oracle's own distance from it."""
-    line = _run_bench("--workload", "c5t", "--steps", "3", "--warmup", "1", "--prime-ms", "5")
+    line = _run_bench("--workload", "c5t", "--steps", "3", "--warmup", "1", "--prime-ms", "5", "--full")
     r = line["roofline"]
     assert line["unit"] == "rows/s" and r["bound"] == "hbm" and "rnvp_bwd_ts" in r["kernel"]
     assert r["launches_timed"] == 3 * 2 and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
@@ -526,10 +526,10 @@ def test_bench_lenet_training_step_line(amd):
 
 
 def test_bench_default_line_carries_the_other_configurations(amd):
-    """The default (driver-run) invocation attaches 20-step runs of c3, c4, c5, c5b, c6, c2t, c3t, c5t and the MNF-LeNet step as `secondary`
+    """The --full invocation of the default workload attaches 20-step runs of c3, c4, c5, c5b, c6, c2t, c3t, c5t and the MNF-LeNet step as `secondary`
     (only c2 used to be driver-observable), the per-step median / min and a one-thread CPU
     figure."""
-    line = _run_bench("--steps", "5", "--warmup", "2", "--prime-ms", "5", "--no-cpu-baseline")
+    line = _run_bench("--steps", "5", "--warmup", "2", "--prime-ms", "5", "--no-cpu-baseline", "--full")
     assert line["config"]["workload"].startswith("9xAffineHalfFlow d=64")
     sec = line["secondary"]
     assert set(sec) == {"c3", "c4", "c5", "c5b", "c6", "c1", "c2_fp32", "c2t", "c3t", "c5t", "lenet"}
@@ -544,7 +544,7 @@ def test_bench_default_line_carries_the_other_configurations(amd):
 
 
 def test_bench_cpu_baseline_has_a_one_thread_figure(amd):
-    line = _run_bench("--steps", "3", "--warmup", "1", "--prime-ms", "5", "--no-secondary")
+    line = _run_bench("--steps", "3", "--warmup", "1", "--prime-ms", "5", "--no-secondary", "--full")
     cb = line["cpu_baseline"]
     assert cb["one_thread"]["value"] > 0 and cb["value"] > 0
     # one thread and many threads measured on the SAME rows

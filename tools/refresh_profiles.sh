@@ -16,7 +16,7 @@ declare -A KERN=( [c2]="ahf_split_stack_kernel<32, 24, true" [c4]="ahf_split_sta
 declare -A MULT=( [c3t]=2 )
 for w in $WL; do
   extra=""; [ "$w" = c2 ] && extra="--no-secondary"
-  timeout 400 python bench.py --workload $w $extra > "$OUT/${w}_bench.json" 2> "$OUT/${w}_bench.err"
+  timeout 400 python bench.py --workload $w --full $extra > "$OUT/${w}_bench.json" 2> "$OUT/${w}_bench.err"
   P=$REPO/gpurun_out/prof_${ROUND}_$w
   mkdir -p "$P"
   ARGS="--steps 20 --warmup 5 --no-cpu-baseline --no-secondary --workload $w"
