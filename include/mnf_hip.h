@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 14
+#define MNF_ABI_VERSION 15
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -624,7 +624,8 @@ int mnf_nsf_cl_bwd_tile_fixup(const float* x, const float* grad_y, const float* 
                               float* grad_flat, const float* flat, int64_t rows, int dim, int K, float tail_bound,
                               int inverse, int n_hidden, const int* hidden_host, const int32_t* cold,
                               int cold_capacity, void* stream);
-/* mnf_nsf_cl_bwd for ANY dim, K = 2 .. 16 and 1 .. 4 hidden layers of widths 4 .. 64 on the f16 matrix pipe
+/* mnf_nsf_cl_bwd for ANY dim, K = 2 .. 16 and 1 .. 4 hidden layers of widths 4 .. 64 (fewer at K >= 9: the weight slot's
+ * limit, see mnf_nsf_cl_bwd_rt_supported) on the f16 matrix pipe
  * (mnf_nsf_bwd_rt.hip: run-time shapes, weights read from `flat`; no operand image, no workspace).  y = the layer's OUTPUT
  * for the same x, direction and parameters; grad_scale_dev as for mnf_nsf_cl_bwd_tile.  grad_x is written, grad_flat ADDED
  * to with float atomics, one flush per block of 16 .. 128 rows and slot (or NULL).  MNF_ERR_UNSUPPORTED: shape outside these
@@ -678,6 +679,28 @@ int mnf_rnvp_bwd_mfma_phases(const float* z, const float* mask, uint64_t seed, c
 int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld, float* grad_z,
                     float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int n_hidden,
                     const int* hidden_host, void* stream);
+/* Shape queries of the run-time-shaped kernels, host only (no GPU needed): 1 where the kernel has a launch for the shape,
+ * 0 where its entry point -- mnf_affine_half / mnf_nsf_cl / mnf_rnvp* for the forward kernels, which then run the VALU
+ * kernel -- refuses it; the launchers answer from the same plan.  Not covered: the row count (with force_generic == 0 the
+ * forward entry points take the kernel from 2,048 rows on; torch_mnf_amd/_dispatch.py decides it for the gradients), the
+ * alignment of the rows (unaligned ones take another variant, never a refusal) and MNF_DETERMINISTIC (the *_bwd_rt
+ * kernels then refuse every shape).  The limits:
+ *   mnf_affine_half_rt_supported      >= 1 hidden layer, widths 4 .. 256, any even dim
+ *   mnf_affine_half_bwd_rt_supported  1 .. 4 hidden layers of widths 4 .. 64, any even dim
+ *   mnf_nsf_cl_rt_supported           K = 2 .. 16, >= 1 hidden layer, widths 4 .. 64, any even dim
+ *   mnf_nsf_cl_bwd_rt_supported       K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 64, any even dim -- and a weight
+ *                                     slot (a slot's output blocks and their turned counterparts) of at most 40 blocks
+ *                                     that fits 160 KB of LDS with the rest.  With equal widths n_h: K <= 8 any n_h;
+ *                                     K = 9 n_h <= 64 (1 - 2 layers) / 48 (3 - 4); K = 10 .. 12 n_h <= 48 / 32;
+ *                                     K = 13 .. 16 n_h <= 32
+ *   mnf_rnvp_rt_supported             >= 1 conditioner layer, widths 4 .. 256, any dim
+ *   mnf_rnvp_bwd_rt_supported         1 .. 4 conditioner layers of widths 4 .. 128, any dim */
+int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
+int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
+int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_nsf_cl_bwd_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_rnvp_rt_supported(int dim, int n_hidden, const int* hidden_host);
+int mnf_rnvp_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host);
 /* AffineConstantFlow: grad_x = grad_y * exp(+-s); grad_s, grad_t (dim,) are ADDED to. */
 int mnf_affine_const_bwd(const float* x, const float* y, const float* grad_y, const float* s,
                          float* grad_x, float* grad_s, float* grad_t, int64_t rows, int dim,

@@ -338,3 +338,35 @@ def test_dispatch_table_agrees_with_the_measured_coverage_map():
     assert _dispatch.tier("ahf", "fwd", 100, 64, (24, 24)) == "valu" and _dispatch.tier("ahf", "fwd", 4096, 64, (24, 24)) == "rt"
     assert _dispatch.tier("rnvp", "bwd", 128, 800, (50,)) == "per-shape" and _dispatch.tier("rnvp", "bwd", 4096, 50, (50,)) == "rt"
     assert _dispatch.tier("nsf", "fwd", 4096, 2, (16,) * 3, 8) == "rt" and _dispatch.tier("nsf", "fwd", 1 << 16, 2, (16,) * 3, 8) == "per-shape"
+
+
+def test_rt_shape_queries_at_the_envelope_edges(lib):
+    """The run-time-shaped kernels' shape queries (mnf_*_rt_supported: the launchers' own plans) at the edges of their
+    envelopes, and tier() following them at 262,144 rows.  The NSF_CL gradient kernel's weight slot limits n_h from K = 9
+    on (include/mnf_hip.h); a shape it refuses runs the VALU gradient kernel."""
+    from torch_mnf_amd import _dispatch, _lib
+
+    arr = _lib.int_array
+    rows = 262144
+    for dim, K, n_h, want in ((128, 16, 64, 0), (128, 16, 48, 0), (128, 16, 32, 1), (16, 16, 16, 1), (128, 13, 33, 0),
+                              (128, 9, 48, 1), (128, 9, 64, 0), (128, 12, 64, 0), (128, 10, 32, 1), (128, 8, 64, 1)):
+        assert lib.mnf_nsf_cl_bwd_rt_supported(dim, K, 3, arr((n_h,) * 3)) == want, (dim, K, n_h)
+        assert lib.mnf_nsf_cl_rt_supported(dim, K, 3, arr((n_h,) * 3)) == 1, (dim, K, n_h)
+        assert _dispatch.tier("nsf", "bwd", rows, dim, (n_h,) * 3, K) == ("rt" if want else "valu"), (dim, K, n_h)
+    assert lib.mnf_nsf_cl_bwd_rt_supported(128, 12, 2, arr((48, 48))) == 1
+    assert lib.mnf_nsf_cl_bwd_rt_supported(128, 9, 2, arr((64, 64))) == 1
+    assert lib.mnf_nsf_cl_rt_supported(128, 17, 3, arr((16,) * 3)) == 0 and lib.mnf_nsf_cl_rt_supported(128, 4, 3, arr((3,) * 3)) == 0
+    # AffineHalfFlow: widths up to 256 forward, 64 (and four layers) backward
+    assert lib.mnf_affine_half_rt_supported(64, 1, arr((300,)), 1, 1) == 0
+    assert lib.mnf_affine_half_bwd_rt_supported(64, 1, arr((300,)), 1, 1) == 0
+    assert _dispatch.tier("ahf", "fwd", rows, 64, (300,)) == "valu" and _dispatch.tier("ahf", "bwd", rows, 64, (300,)) == "valu"
+    assert lib.mnf_affine_half_rt_supported(64, 2, arr((256, 4)), 1, 0) == 1
+    assert lib.mnf_affine_half_bwd_rt_supported(64, 4, arr((64,) * 4), 0, 1) == 1
+    assert lib.mnf_affine_half_bwd_rt_supported(64, 5, arr((64,) * 5), 1, 1) == 0
+    assert lib.mnf_affine_half_rt_supported(64, 1, arr((24,)), 0, 0) == 0
+    # RNVP: widths up to 256 forward, 128 backward
+    assert lib.mnf_rnvp_rt_supported(100, 1, arr((200,))) == 1 and lib.mnf_rnvp_bwd_rt_supported(100, 1, arr((200,))) == 0
+    assert _dispatch.tier("rnvp", "fwd", rows, 100, (200,)) == "rt" and _dispatch.tier("rnvp", "bwd", rows, 100, (200,)) == "valu"
+    assert lib.mnf_rnvp_bwd_rt_supported(100, 4, arr((128,) * 4)) == 1
+    # malformed shapes are refused, not read past
+    assert lib.mnf_rnvp_rt_supported(100, 0, None) == 0 and lib.mnf_affine_half_rt_supported(63, 1, arr((24,)), 1, 1) == 0

@@ -429,3 +429,41 @@ def test_graphed_training_step_of_a_model_on_the_run_time_shaped_kernels(amd):
         opt.step()
         first = float(loss.detach()) if first is None else first
     assert float(loss.detach()) < first
+
+
+# the edges of the run-time-shaped kernels' envelopes (include/mnf_hip.h mnf_*_rt_supported): (layer, dim, shape)
+RT_EDGE_SHAPES = [("nsf", 128, (16, 64)), ("nsf", 128, (16, 32)), ("nsf", 16, (16, 16)), ("nsf", 128, (9, 64)),
+                  ("nsf", 128, (9, 48)), ("ahf", 64, (300,)), ("ahf", 64, (64,) * 5), ("rnvp", 100, (200,)),
+                  ("rnvp", 100, (128, 128))]
+
+
+@pytest.mark.parametrize("kind,dim,shape", RT_EDGE_SHAPES, ids=lambda v: str(v).replace(" ", ""))
+def test_tier_names_the_kernel_that_runs_at_the_envelope_edges(amd, kind, dim, shape):
+    """_dispatch.tier() -- the library's shape queries -- names the tier of the kernel the layer actually runs, forward and
+    gradient, at the edges of the run-time-shaped kernels' shapes (NSF_CL K = 16 / n_h = 64: the gradient kernel's weight
+    slot does not fit, the VALU gradient kernel runs)."""
+    rows = 4096
+    if kind == "nsf":
+        K, n_h = shape
+        f, hidden, call = amd.NSF_CL(dim, K=K, B=3, n_h=n_h), (n_h,) * 3, lambda m, x: m.inverse(x)
+    elif kind == "ahf":
+        K, hidden, call = None, shape, lambda m, x: m.inverse(x)
+        f = amd.AffineHalfFlow(dim, parity=False, h_sizes=shape)
+    else:
+        K, hidden, call = None, shape, lambda m, x: m.forward(x, seed=3)
+        f = amd.RNVP(dim, h_sizes=shape)
+    f = f.to(DEV)
+    x = torch.randn(rows, dim, device=DEV)
+    with torch.no_grad():
+        call(f, x)
+    k_fwd = amd.last_kernel()
+    xg = x.clone().requires_grad_(True)
+    y, ld = call(f, xg)
+    (y.sum() + ld.sum()).backward()
+    torch.cuda.synchronize()
+    k_bwd = amd.last_kernel()
+    want_bwd = amd._dispatch.tier(kind, "bwd", rows, dim, hidden, K)
+    if amd.deterministic() and want_bwd == "rt":  # (the *_bwd_rt kernels refuse under MNF_DETERMINISTIC=1)
+        want_bwd = "valu"
+    assert amd._dispatch.tier_of_kernel(k_fwd) == amd._dispatch.tier(kind, "fwd", rows, dim, hidden, K), k_fwd
+    assert amd._dispatch.tier_of_kernel(k_bwd) == want_bwd, k_bwd

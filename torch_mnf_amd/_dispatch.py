@@ -23,7 +23,7 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | >= RT_MIN_ROWS  | any d, K 2..16, hidden widths 4..64               | nsf_rt                         |
 |                          | else            | anything                                          | nsf_generic                    |
 | NSF_CL bwd               | any             | the tile kernel's shapes                          | nsf_bwd_tile (+ fix-up)        |
-|                          | >= RT_MIN_ROWS  | any d, K 2..16, 1..4 hidden layers of widths 4..64 | nsf_bwd_rt                    |
+|                          | >= RT_MIN_ROWS  | any d, K 2..16, 1..4 layers 4..64, LDS slot (*)   | nsf_bwd_rt                     |
 |                          | else            | anything                                          | nsf_bwd_generic                |
 | RNVP fwd                 | few (C side)    | one hidden layer <= 64                            | rnvp_few                       |
 |                          | any             | one hidden layer <= 64, d >= 49                   | rnvp_resident / narrow / split |
@@ -33,6 +33,10 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | not rnvp_bwd_small() | one hidden layer <= 64, padded d >= 64       | rnvp_bwd_mfma                  |
 |                          | >= RT_MIN_ROWS  | 1..4 layers of widths 4..128, any d               | rnvp_bwd_rt                    |
 |                          | else            | anything                                          | rnvp_bwd_generic               |
+
+The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
+NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
+layer, K <= 8 takes n_h <= 64; K = 9 n_h <= 64 at 1-2 layers, 48 at 3-4; K = 10..12 n_h <= 48 / 32; K = 13..16 n_h <= 32.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and
@@ -87,14 +91,11 @@ def rnvp_bwd_small(rows: int, dim: int) -> bool:
 # tests/test_abi_symbols.py checks it against every row of the committed coverage map (profiles/r6/coverage_map.txt):
 # the table, this function and the measured map cannot drift apart unnoticed.
 # ---------------------------------------------------------------------------------------------------------------------
-def _rt_range(kind: str, direction: str, hidden, K) -> bool:
-    if not hidden or min(hidden) < 4:
-        return False
-    if kind == "ahf":
-        return max(hidden) <= (256 if direction == "fwd" else 64) and (direction == "fwd" or len(hidden) <= 4)
-    if kind == "nsf":
-        return max(hidden) <= 64 and K is not None and 2 <= K <= 16 and (direction == "fwd" or len(hidden) <= 4)
-    return max(hidden) <= (256 if direction == "fwd" else 128) and (direction == "fwd" or len(hidden) <= 4)
+def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> bool:
+    """True where a call without a per-shape kernel goes to the run-time-shaped kernels if they have its shape (the
+    gradient passes ask here; the C entry points decide it the same way for the forward kernels): from RT_MIN_ROWS rows
+    on, not under an fp32 request (their arithmetic is split-f16); force_generic = 1 / 2: never / at any row count."""
+    return force_generic != 1 and (force_generic == 2 or (rows >= RT_MIN_ROWS and not fp32_request))
 
 
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
@@ -120,7 +121,17 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
             per_shape = per_shape and not rnvp_bwd_small(rows, dim)
     if per_shape:
         return "per-shape"
-    return "rt" if rows >= RT_MIN_ROWS and _rt_range(kind, direction, hidden, K) else "valu"
+    if not wants_rt(rows):
+        return "valu"
+    fwd = direction == "fwd"
+    if kind == "ahf":
+        query = lib.mnf_affine_half_rt_supported if fwd else lib.mnf_affine_half_bwd_rt_supported
+        rt = query(dim, n, hid, int(scale), int(shift))
+    elif kind == "nsf":
+        rt = (lib.mnf_nsf_cl_rt_supported if fwd else lib.mnf_nsf_cl_bwd_rt_supported)(dim, K, n, hid)
+    else:
+        rt = (lib.mnf_rnvp_rt_supported if fwd else lib.mnf_rnvp_bwd_rt_supported)(dim, n, hid)
+    return "rt" if rt else "valu"
 
 
 def tier_of_kernel(name: str) -> str:

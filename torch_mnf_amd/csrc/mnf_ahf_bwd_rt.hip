@@ -190,9 +190,63 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
   }
 }
 
+// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.
+static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, AhfBwdRtArgs& a,
+                            RtPlan& p) {
+  if (dim < 2 || (dim & 1) || n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || !hidden_ok(n_hidden, hidden) ||
+      (!has_scale && !has_shift))
+    return false;
+  const int H = dim / 2;
+  int sizes[MNF_MAX_LINEAR + 1];
+  sizes[0] = H;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  sizes[n_hidden + 1] = H;
+  if (w.min < 4 || w.max > 64) return false;
+  int64_t off = 0;
+  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
+  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
+  if (!has_scale) a.s_net = a.t_net;
+  if (!has_shift) a.t_net = a.s_net;
+  if (off >= (1ll << 31)) return false;
+  a.n_params = (int)off;
+  p.mt_max = 4;
+  a.bt = 8;
+  a.bias_words = 2 * a.bt * 16;
+  a.ht_tiles = w.tiles;
+  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
+  const int KS1 = (16 * ((hidden[0] + 15) / 16) + 31) / 32;
+  // The LDS plan.  Rows per workgroup first (16 per wave, any wave count: the per-row-block cost is what this kernel is
+  // bound by), then the roomier of two weight-stream sizes (12 blocks per buffer: fewer chunks; 8: the largest chunk
+  // there is -- two output tiles' forward blocks and the transposed blocks of their K-step at 64 hidden units), then as
+  // many first-layer input tiles per chunk as fit (the output-layer chunks need two).
+  for (p.nw = 8; p.nw >= 1; --p.nw) {
+    for (int cb = 12; cb >= 8; cb -= 4) {
+      int ci = cb / KS1;
+      ci = ci > p.mt_max ? p.mt_max : ci < 2 ? 2 : ci;
+      for (int ct = ci; ct >= 2; ct = ct > 2 ? 2 : 0) {
+        p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)2 * cb * rt::kBlockWords * 4 + (size_t)a.bias_words * 4 +
+                rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, ct);
+        if (p.lds <= 160 * 1024) {
+          a.cb = cb;
+          a.block_words = 2 * cb * rt::kBlockWords;
+          a.ct_tiles = ct;
+          return true;
+        }
+      }
+    }
+  }
+  return false;
+}
+
 }  // namespace mnf
 
 using namespace mnf;
+
+extern "C" int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
+  AhfBwdRtArgs a;
+  RtPlan p;
+  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p) ? 1 : 0;
+}
 
 extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
                                       float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
@@ -201,82 +255,16 @@ extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const floa
   if (!x || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || (!has_scale && !has_shift) || (inverse && has_scale && !y) ||
-      deterministic() || rows * dim >= (1ll << 40))
-    return MNF_ERR_UNSUPPORTED;
+  if ((inverse && has_scale && !y) || deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   AhfBwdRtArgs a;
   memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p)) return MNF_ERR_UNSUPPORTED;
   a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
   a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity != 0; a.inverse = inverse != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
-  const int H = dim / 2;
-  int sizes[MNF_MAX_LINEAR + 1];
-  sizes[0] = H;
-  int mn = 1 << 30, mxh = 0, ht = 0, dt = 0;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-    mxh = hidden[i] > mxh ? hidden[i] : mxh;
-    ht += (hidden[i] + 15) / 16;
-    dt = (hidden[i] + 15) / 16 > dt ? (hidden[i] + 15) / 16 : dt;
-  }
-  sizes[n_hidden + 1] = H;
-  if (mn < 4 || mxh > 64) return MNF_ERR_UNSUPPORTED;
-  int64_t off = 0;
-  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
-  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
-  if (!has_scale) a.s_net = a.t_net;
-  if (!has_shift) a.t_net = a.s_net;
-  if (off >= (1ll << 31)) return MNF_ERR_UNSUPPORTED;
-  a.n_params = (int)off;
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  a.vec = dim % 8 == 0 && aligned(x) && aligned(grad_x) && (!y || aligned(y)) && (!grad_y || aligned(grad_y));
-  constexpr int MT_MAX = 4;
-  a.bt = 8;
-  a.bias_words = 2 * a.bt * 16;
-  a.ht_tiles = ht;
-  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
-  (void)dt;
-  const int KS1 = (16 * ((hidden[0] + 15) / 16) + 31) / 32;
-  // The LDS plan.  Rows per workgroup first (16 per wave, any wave count: the per-row-block cost is what this kernel is
-  // bound by), then the roomier of two weight-stream sizes (12 blocks per buffer: fewer chunks; 8: the largest chunk
-  // there is -- two output tiles' forward blocks and the transposed blocks of their K-step at 64 hidden units), then as
-  // many first-layer input tiles per chunk as fit (the output-layer chunks need two).
-  int nw = 8;
-  size_t lds = 0;
-  bool fits = false;
-  for (; nw >= 1; --nw) {
-    const size_t tile_bytes = (size_t)2 * 16 * (16 * nw + rt::kExPad) * 2;
-    for (int cb = 12; cb >= 8 && !fits; cb -= 4) {
-      int ci = cb / KS1;
-      ci = ci > MT_MAX ? MT_MAX : ci < 2 ? 2 : ci;
-      for (int ct = ci; ct >= 2 && !fits; ct = ct > 2 ? 2 : 0) {
-        lds = (size_t)4 * rt::kBwdHeadWords + (size_t)2 * cb * rt::kBlockWords * 4 + (size_t)a.bias_words * 4 +
-              (size_t)(a.ht_tiles + a.dt_tiles + ct) * tile_bytes + (size_t)nw * (rt::kMaxBwdLayers + 1) * 64 * 4;
-        if (lds <= 160 * 1024) {
-          a.cb = cb;
-          a.ct_tiles = ct;
-          fits = true;
-        }
-      }
-    }
-    if (fits) break;
-  }
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  if (nw < 1) return MNF_ERR_UNSUPPORTED;
-  auto kernel = ahf_bwd_rt_kernel<MT_MAX>;
+  a.vec = dim % 8 == 0 && aligned16(x, grad_x, y, grad_y);
   static DeviceMemo attr;
-  attr.get([&](int) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_bwd_rt_kernel<MT_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    return 1;
-  });
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t need = (rows + 16 * nw - 1) / (16 * nw);
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  tag_kernel("ahf_bwd_rt");
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, (hipStream_t)stream, a);
-  return check_launch();
+  allow_big_lds(attr, ahf_bwd_rt_kernel<4>);
+  return launch_persistent(ahf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "ahf_bwd_rt", (hipStream_t)stream);
 }

@@ -212,112 +212,85 @@ __global__ void __launch_bounds__(NW * 64) ahf_rt_kernel(AhfRtArgs a) {
   }
 }
 
-// blocks and bias tiles of the whole conditioner (the resident image), and the largest hidden width
-static void ahf_rt_plan(const NetDesc& nd, int H, int heads, int64_t& n_blocks, int64_t& n_bias, int& max_hidden) {
-  n_blocks = 0;
-  n_bias = 0;
-  max_hidden = 0;
-  const int L = nd.n_lin - 1;
-  for (int l = 0; l < L; ++l) {
-    const int in_cols = l == 0 ? nd.sizes[0] : 16 * ((nd.sizes[l] + 15) / 16);
-    const int KS = (in_cols + 31) / 32, MT = (nd.sizes[l + 1] + 15) / 16;
+// The launch of a shape (`aligned`: x and y 16-byte aligned), or false: the VALU kernel takes it.  Fills the kernel
+// arguments' shape part.
+static bool ahf_rt_plan(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, bool aligned, AhfRtArgs& a,
+                        RtPlan& p) {
+  if (dim < 2 || (dim & 1) || n_hidden < 1 || !hidden_ok(n_hidden, hidden) || (!has_scale && !has_shift)) return false;
+  const int H = dim / 2;
+  int sizes[MNF_MAX_LINEAR + 1];
+  sizes[0] = H;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  sizes[n_hidden + 1] = H;
+  // (widths < 4: a sum of one or two split products is not a 1e-5 sum, flows.py _MIN_SPLIT_HIDDEN)
+  if (w.min < 4 || w.max > 256) return false;
+  int64_t off = 0;
+  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
+  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
+  if (!has_scale) a.s_net = a.t_net;
+  if (!has_shift) a.t_net = a.s_net;
+  if (off >= (1ll << 31)) return false;
+  a.n_params = (int)off;
+  a.vec = dim % 8 == 0 && aligned;
+  // blocks and bias tiles of the whole conditioner (the resident image)
+  const int heads = (has_scale ? 1 : 0) + (has_shift ? 1 : 0);
+  int64_t n_blocks = 0, n_bias = 0;
+  for (int l = 0; l <= n_hidden; ++l) {
+    const int in_cols = l == 0 ? H : 16 * ((sizes[l] + 15) / 16);
+    const int KS = (in_cols + 31) / 32, MT = (sizes[l + 1] + 15) / 16;
     n_blocks += (int64_t)heads * KS * MT;
     n_bias += (int64_t)heads * MT;
-    if (nd.sizes[l + 1] > max_hidden) max_hidden = nd.sizes[l + 1];
   }
-  const int KS = (16 * ((nd.sizes[L] + 15) / 16) + 31) / 32, M = (H + 15) / 16;
-  n_blocks += (int64_t)heads * KS * M;
-  n_bias += (int64_t)heads * M;
-}
-
-template <typename K>
-static void rt_allow_big_lds(K kernel) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <int MT_MAX, int NTL, int NW>
-static int ahf_rt_launch_class(AhfRtArgs& a, int64_t n_blocks, int64_t n_bias, hipStream_t stream) {
-  constexpr int kResidentBytes = 158 * 1024, kStreamBlocks = 16, kStreamBias = 16;
-  const int64_t resident_bytes = n_blocks * 2048 + n_bias * 64;
   // Rows that are not 16-byte aligned (dim not a multiple of 8, a view at an odd offset) have the resident variant only,
   // except in the widest class, whose streaming kernel takes the alignment at run time (a branch around every row access:
-  // 15-20 % on the memory-bound shapes) and serves every width: ahf_rt_launch sends such a call there.
-  const bool resident = resident_bytes <= kResidentBytes;
+  // 15-20 % on the memory-bound shapes) and serves every width: such a call goes there.
+  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
+  p.resident = n_blocks * 2048 + n_bias * 64 <= 158 * 1024;
+  p.mt_max = !p.resident && !a.vec ? 16 : w.max <= 64 ? 4 : w.max <= 128 ? 8 : 16;
+  a.cb = p.resident ? (int)n_blocks : kStream;
+  a.bt = p.resident ? (int)n_bias : kStream;
+  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
+  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
+  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
+  // workgroups of 8 waves (4 in the widest class) -- of 4 when the LDS footprint lets a CU hold two or more of them (they
+  // overlap each other's barriers, staging and memory waits; streaming: every wave of the CU shares one conversion of the
+  // weights)
+  p.nw = p.mt_max == 16 || (p.resident && p.lds <= 79 * 1024) ? 4 : 8;
+  return true;
+}
+
+template <int MT_MAX, int NW>
+static int ahf_rt_launch_class(const AhfRtArgs& a, const RtPlan& p, hipStream_t stream) {
   constexpr int kStreamVec = MT_MAX == 16 ? 2 : 1;
-  if (!resident && !a.vec && kStreamVec != 2) return MNF_ERR_UNSUPPORTED;
-  if (resident) {
-    a.cb = (int)n_blocks;
-    a.bt = (int)n_bias;
-    a.block_words = (int)n_blocks * rt::kBlockWords;
-    a.bias_words = (int)n_bias * 16;
-  } else {
-    a.cb = kStreamBlocks;
-    a.bt = kStreamBias;
-    a.block_words = 2 * kStreamBlocks * rt::kBlockWords;
-    a.bias_words = 2 * kStreamBias * 16;
-  }
-  const size_t lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
   static DeviceMemo attr;
-  attr.get([&](int) {
-    rt_allow_big_lds(ahf_rt_kernel<MT_MAX, NTL, NW, true, 1>);
-    rt_allow_big_lds(ahf_rt_kernel<MT_MAX, NTL, NW, false, kStreamVec>);
-    rt_allow_big_lds(ahf_rt_kernel<MT_MAX, NTL, NW, true, 0>);
-    return 1;
-  });
-  // workgroups of NW waves -- of 4 when the LDS footprint lets a CU hold two or more of them (they overlap each other's
-  // barriers, staging and memory waits); persistent grid = what the occupancy query says is resident
-  auto kernel = !resident ? ahf_rt_kernel<MT_MAX, NTL, NW, false, kStreamVec>
-                          : a.vec ? ahf_rt_kernel<MT_MAX, NTL, NW, true, 1> : ahf_rt_kernel<MT_MAX, NTL, NW, true, 0>;
-  const int nw = NW == 8 && resident && lds <= 79 * 1024 ? 4 : NW;  // (streaming: every wave of the CU shares one conversion of the weights)
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t rows_per_block = (int64_t)nw * NTL * 16;
-  const int64_t need = (a.rows + rows_per_block - 1) / rows_per_block;
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
-  return check_launch();
+  allow_big_lds(attr, ahf_rt_kernel<MT_MAX, 1, NW, true, 1>, ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>,
+                ahf_rt_kernel<MT_MAX, 1, NW, true, 0>);
+  auto kernel = !p.resident ? ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>
+                            : a.vec ? ahf_rt_kernel<MT_MAX, 1, NW, true, 1> : ahf_rt_kernel<MT_MAX, 1, NW, true, 0>;
+  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, "ahf_rt", stream);
 }
 
 // MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
 int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const float* flat, int64_t rows,
                   int dim, int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
                   hipStream_t stream) {
-  if (!flat || n_hidden < 1 || (!has_scale && !has_shift) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  if (!flat || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   AhfRtArgs a;
   memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, aligned16(x, y), a, p)) return MNF_ERR_UNSUPPORTED;
   a.x = x; a.y = y; a.log_det = log_det; a.ysq = ysq; a.flat = flat; a.rows = rows; a.dim = dim;
   a.parity = parity != 0; a.inverse = inverse != 0; a.accumulate = accumulate != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
-  const int H = dim / 2;
-  int sizes[MNF_MAX_LINEAR + 1];
-  sizes[0] = H;
-  int mn = 1 << 30;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-  }
-  sizes[n_hidden + 1] = H;
-  if (mn < 4) return MNF_ERR_UNSUPPORTED;  // a sum of one or two split products is not a 1e-5 sum (flows.py _MIN_SPLIT_HIDDEN)
-  int64_t off = 0;
-  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
-  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
-  if (!has_scale) a.s_net = a.t_net;
-  if (!has_shift) a.t_net = a.s_net;
-  if (off >= (1ll << 31)) return MNF_ERR_UNSUPPORTED;
-  a.n_params = (int)off;
-  a.vec = dim % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-  int64_t n_blocks, n_bias;
-  int max_hidden;
-  const int heads = (has_scale ? 1 : 0) + (has_shift ? 1 : 0);
-  ahf_rt_plan(a.s_net, H, heads, n_blocks, n_bias, max_hidden);
-  tag_kernel("ahf_rt");
-  if (max_hidden > 256) return MNF_ERR_UNSUPPORTED;
-  int rc = MNF_ERR_UNSUPPORTED;
-  if (max_hidden <= 64) rc = ahf_rt_launch_class<4, 1, 8>(a, n_blocks, n_bias, stream);
-  else if (max_hidden <= 128) rc = ahf_rt_launch_class<8, 1, 8>(a, n_blocks, n_bias, stream);
-  if (rc == MNF_ERR_UNSUPPORTED) rc = ahf_rt_launch_class<16, 1, 4>(a, n_blocks, n_bias, stream);
-  return rc;
+  if (p.mt_max == 4) return ahf_rt_launch_class<4, 8>(a, p, stream);
+  if (p.mt_max == 8) return ahf_rt_launch_class<8, 8>(a, p, stream);
+  return ahf_rt_launch_class<16, 4>(a, p, stream);
 }
 
 }  // namespace mnf
+
+extern "C" int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
+  mnf::AhfRtArgs a;
+  mnf::RtPlan p;
+  return mnf::ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+}

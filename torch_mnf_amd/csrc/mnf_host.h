@@ -102,6 +102,59 @@ inline int64_t balanced_grid(int64_t n_tiles, int waves_per_block, int resident_
 // The run-time-shaped matrix-core kernels (mnf_rt.h: any layer count and widths, weights from `flat`) take a call from this
 // many rows on; below, the VALU any-shape kernels of mnf_generic.hip (one workgroup per few rows) have the lower latency.
 constexpr int64_t kRtMinRows = 2048;
+
+// Host side of their launchers (mnf_*_rt.hip).  Each has a plan function of the shape alone -- false where the kernel has
+// no launch for the shape, else the kernel arguments' shape part and an RtPlan -- which its mnf_*_rt_supported query
+// answers from too.
+struct RtPlan {
+  int mt_max;     // size class: hidden tiles of a vector (4 / 8 / 16: widths up to 64 / 128 / 256)
+  bool resident;  // forward kernels: the whole conditioner staged into LDS once (else chunk by chunk)
+  int nw;         // waves per workgroup
+  size_t lds;     // dynamic LDS bytes
+};
+// sizes[1 .. n_hidden] := hidden[]; the smallest and largest width and the 16-unit tiles of all of them
+struct HiddenWidths {
+  int min, max, tiles;
+};
+inline HiddenWidths scan_hidden(int n_hidden, const int* hidden, int* sizes) {
+  HiddenWidths w{1 << 30, 0, 0};
+  for (int i = 0; i < n_hidden; ++i) {
+    sizes[1 + i] = hidden[i];
+    w.min = hidden[i] < w.min ? hidden[i] : w.min;
+    w.max = hidden[i] > w.max ? hidden[i] : w.max;
+    w.tiles += (hidden[i] + 15) / 16;
+  }
+  return w;
+}
+// every pointer 16-byte aligned (a null one is): the kernels' dwordx4 row accesses
+template <typename... P>
+inline bool aligned16(const P*... p) {
+  return (((reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
+}
+// up to 160 KB of dynamic LDS for each of `kernels`, set once per device (`memo`: the call site's own)
+template <typename... K>
+inline void allow_big_lds(DeviceMemo& memo, K... kernels) {
+  memo.get([&](int) {
+    ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
+     ...);
+    return 1;
+  });
+}
+// persistent grid: as many workgroups of nw waves as the occupancy query says are resident (one per CU if it fails), at
+// most one per `rows_per_block` rows; tags the launch with the kernel family `tag`
+template <typename Args>
+inline int launch_persistent(void (*kernel)(Args), const Args& a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
+                             const char* tag, hipStream_t stream) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+  const int64_t need = (rows + rows_per_block - 1) / rows_per_block;
+  int64_t grid = (int64_t)per_cu * device_cus(current_device());
+  if (grid > need) grid = need;
+  tag_kernel(tag);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
+  return check_launch();
+}
+
 int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const float* flat, int64_t rows,
                   int dim, int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
                   hipStream_t stream);

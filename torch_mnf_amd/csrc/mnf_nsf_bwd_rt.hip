@@ -265,9 +265,47 @@ __global__ void __launch_bounds__(512) nsf_bwd_rt_kernel(NsfBwdRtArgs a) {
   }
 }
 
+// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.
+static bool nsf_bwd_rt_plan(int dim, int K, int n_hidden, const int* hidden, NsfBwdRtArgs& a, RtPlan& p) {
+  if (dim < 2 || (dim & 1) || K < 2 || K > 16 || n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || !hidden_ok(n_hidden, hidden))
+    return false;
+  const int H = dim / 2, P = 3 * K - 1;
+  int sizes[MNF_MAX_LINEAR + 1];
+  sizes[0] = H;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  sizes[n_hidden + 1] = P * H;
+  if (w.min < 4 || w.max > 64 || (int64_t)P * H * w.max >= (1ll << 30)) return false;
+  int64_t off = fill_net(a.f1, n_hidden + 2, sizes, 0);
+  off += fill_net(a.f2, n_hidden + 2, sizes, off);
+  a.n_params = (int)off;
+  p.mt_max = 4;
+  const int TV = nsfb_tiles(K), MTh = (hidden[n_hidden - 1] + 15) / 16, KS = (16 * MTh + 31) / 32, KSO = (TV + 1) / 2;
+  a.cb = TV * KS + KSO * MTh;  // a slot: its output tiles' blocks and their turned counterparts
+  if (a.cb < 8) a.cb = 8;
+  if (a.cb > 40) return false;
+  a.bt = TV > p.mt_max ? TV : p.mt_max;
+  a.block_words = 2 * a.cb * rt::kBlockWords;
+  a.bias_words = 2 * a.bt * 16;
+  a.ht_tiles = w.tiles;
+  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
+  a.ct_tiles = TV > p.mt_max ? TV : p.mt_max;
+  for (p.nw = 8; p.nw >= 1; --p.nw) {  // (any wave count: 6 or 7 waves where 8 do not fit)
+    p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
+            rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, a.ct_tiles);
+    if (p.lds <= 160 * 1024) return true;
+  }
+  return false;
+}
+
 }  // namespace mnf
 
 using namespace mnf;
+
+extern "C" int mnf_nsf_cl_bwd_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
+  NsfBwdRtArgs a;
+  RtPlan p;
+  return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
+}
 
 extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
                                  float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
@@ -277,63 +315,15 @@ extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* gr
     return MNF_ERR_INVALID_ARG;
   if (1e-3 * K > 1.0) return MNF_ERR_DOMAIN;
   if (rows == 0) return MNF_OK;
-  if (n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || K < 2 || K > 16 || deterministic() || rows * dim >= (1ll << 40))
-    return MNF_ERR_UNSUPPORTED;
+  if (deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   NsfBwdRtArgs a;
   memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
   a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
   a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound; a.inverse = inverse != 0;
-  const int H = dim / 2, P = 3 * K - 1;
-  int sizes[MNF_MAX_LINEAR + 1];
-  sizes[0] = H;
-  int mn = 1 << 30, mxh = 0, ht = 0, dt = 0;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-    mxh = hidden[i] > mxh ? hidden[i] : mxh;
-    ht += (hidden[i] + 15) / 16;
-    dt = (hidden[i] + 15) / 16 > dt ? (hidden[i] + 15) / 16 : dt;
-  }
-  sizes[n_hidden + 1] = P * H;
-  if (mn < 4 || mxh > 64 || (int64_t)P * H * mxh >= (1ll << 30)) return MNF_ERR_UNSUPPORTED;
-  int64_t off = fill_net(a.f1, n_hidden + 2, sizes, 0);
-  off += fill_net(a.f2, n_hidden + 2, sizes, off);
-  a.n_params = (int)off;
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  a.vec = dim % 8 == 0 && aligned(x) && aligned(y) && aligned(grad_x) && (!grad_y || aligned(grad_y));
-  constexpr int MT_MAX = 4;
-  const int TV = nsfb_tiles(K), MTh = (hidden[n_hidden - 1] + 15) / 16, KS = (16 * MTh + 31) / 32, KSO = (TV + 1) / 2;
-  a.cb = TV * KS + KSO * MTh;  // a slot: its output tiles' blocks and their turned counterparts
-  if (a.cb < 8) a.cb = 8;
-  if (a.cb > 40) return MNF_ERR_UNSUPPORTED;
-  a.bt = TV > MT_MAX ? TV : MT_MAX;
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
-  a.ht_tiles = ht;
-  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
-  (void)dt;
-  a.ct_tiles = TV > MT_MAX ? TV : MT_MAX;
-  int nw = 8;
-  size_t lds = 0;
-  for (; nw >= 1; --nw) {  // (any wave count: 6 or 7 waves where 8 do not fit)
-    lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
-          rt::bwd_lds_bytes(nw, a.ht_tiles, a.dt_tiles, a.ct_tiles);
-    if (lds <= 160 * 1024) break;
-  }
-  if (nw < 1) return MNF_ERR_UNSUPPORTED;
-  auto kernel = nsf_bwd_rt_kernel<MT_MAX>;
+  a.vec = dim % 8 == 0 && aligned16(x, y, grad_x, grad_y);
   static DeviceMemo attr;
-  attr.get([&](int) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(nsf_bwd_rt_kernel<MT_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    return 1;
-  });
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t need = (rows + 16 * nw - 1) / (16 * nw);
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  tag_kernel("nsf_bwd_rt");
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, (hipStream_t)stream, a);
-  return check_launch();
+  allow_big_lds(attr, nsf_bwd_rt_kernel<4>);
+  return launch_persistent(nsf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "nsf_bwd_rt", (hipStream_t)stream);
 }

@@ -195,34 +195,20 @@ __global__ void __launch_bounds__(NW * 64) nsf_rt_kernel(NsfRtArgs a) {
   }
 }
 
-template <typename K>
-static void nsf_rt_allow_big_lds(K kernel) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-// MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
-int nsf_rt_launch(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim, int K,
-                  float tail_bound, int inverse, int n_hidden, const int* hidden, hipStream_t stream) {
-  if (!flat || n_hidden < 1 || K < 2 || K > 16 || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
-  NsfRtArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound;
-  a.inverse = inverse != 0; a.accumulate = accumulate != 0;
+// The launch of a shape (`aligned`: x and y 16-byte aligned), or false: the VALU kernel takes it.  Fills the kernel
+// arguments' shape part.
+static bool nsf_rt_plan(int dim, int K, int n_hidden, const int* hidden, bool aligned, NsfRtArgs& a, RtPlan& p) {
+  if (dim < 2 || (dim & 1) || K < 2 || K > 16 || n_hidden < 1 || !hidden_ok(n_hidden, hidden)) return false;
   const int H = dim / 2, P = 3 * K - 1;
   int sizes[MNF_MAX_LINEAR + 1];
   sizes[0] = H;
-  int mn = 1 << 30, mxh = 0;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-    mxh = hidden[i] > mxh ? hidden[i] : mxh;
-  }
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   sizes[n_hidden + 1] = P * H;  // spline_flow.py:246
-  if (mn < 4 || mxh > 64 || (int64_t)P * H * mxh >= (1ll << 30)) return MNF_ERR_UNSUPPORTED;
+  if (w.min < 4 || w.max > 64 || (int64_t)P * H * w.max >= (1ll << 30)) return false;
   int64_t off = fill_net(a.f1, n_hidden + 2, sizes, 0);
   off += fill_net(a.f2, n_hidden + 2, sizes, off);
   a.n_params = (int)off;
-  a.vec = dim % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
+  a.vec = dim % 8 == 0 && aligned;
   // the resident image: both nets, blocks and bias tiles
   int64_t n_blocks = 0, n_bias = 0;
   for (int l = 0; l < n_hidden; ++l) {
@@ -235,39 +221,39 @@ int nsf_rt_launch(const float* x, float* y, float* log_det, int accumulate, cons
   n_bias += (int64_t)S * TV;
   n_blocks *= 2;
   n_bias *= 2;
-  constexpr int kResidentBytes = 150 * 1024, kStreamBlocks = 24, kStreamBias = 24;
-  const bool resident = n_blocks * 2048 + n_bias * 64 <= kResidentBytes;
-  if (resident) {
-    a.cb = (int)n_blocks;
-    a.bt = (int)n_bias;
-    a.block_words = (int)n_blocks * rt::kBlockWords;
-    a.bias_words = (int)n_bias * 16;
-  } else {
-    if (TV * KS > kStreamBlocks) return MNF_ERR_UNSUPPORTED;
-    a.cb = kStreamBlocks;
-    a.bt = kStreamBias;
-    a.block_words = 2 * kStreamBlocks * rt::kBlockWords;
-    a.bias_words = 2 * kStreamBias * 16;
-  }
-  const size_t lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
-  constexpr int NW = 8;
+  constexpr int kStream = 24;  // blocks and bias tiles per streaming buffer
+  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
+  if (!p.resident && TV * KS > kStream) return false;
+  p.mt_max = 4;
+  a.cb = p.resident ? (int)n_blocks : kStream;
+  a.bt = p.resident ? (int)n_bias : kStream;
+  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
+  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
+  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
+  p.nw = p.resident && p.lds <= 79 * 1024 ? 4 : 8;
+  return true;
+}
+
+// MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
+int nsf_rt_launch(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim, int K,
+                  float tail_bound, int inverse, int n_hidden, const int* hidden, hipStream_t stream) {
+  if (!flat || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  NsfRtArgs a;
+  memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!nsf_rt_plan(dim, K, n_hidden, hidden, aligned16(x, y), a, p)) return MNF_ERR_UNSUPPORTED;
+  a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound;
+  a.inverse = inverse != 0; a.accumulate = accumulate != 0;
   static DeviceMemo attr;
-  attr.get([&](int) {
-    nsf_rt_allow_big_lds(nsf_rt_kernel<4, NW, true>);
-    nsf_rt_allow_big_lds(nsf_rt_kernel<4, NW, false>);
-    return 1;
-  });
-  auto kernel = resident ? nsf_rt_kernel<4, NW, true> : nsf_rt_kernel<4, NW, false>;
-  const int nw = resident && lds <= 79 * 1024 ? 4 : NW;
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t rows_per_block = (int64_t)nw * 16;
-  const int64_t need = (rows + rows_per_block - 1) / rows_per_block;
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  tag_kernel("nsf_rt");
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
-  return check_launch();
+  allow_big_lds(attr, nsf_rt_kernel<4, 8, true>, nsf_rt_kernel<4, 8, false>);
+  auto kernel = p.resident ? nsf_rt_kernel<4, 8, true> : nsf_rt_kernel<4, 8, false>;
+  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "nsf_rt", stream);
 }
 
 }  // namespace mnf
+
+extern "C" int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
+  mnf::NsfRtArgs a;
+  mnf::RtPlan p;
+  return mnf::nsf_rt_plan(dim, K, n_hidden, hidden, true, a, p) ? 1 : 0;
+}

@@ -185,46 +185,59 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
   }
 }
 
-template <int MT_MAX>
-static int rnvp_bwd_rt_launch_class(RnvpBwdRtArgs& a, int max_nw, hipStream_t stream) {
-  // rows per workgroup first (any wave count), then as many first-layer input tiles per chunk as still fit (a.ct_tiles on
-  // entry; the output-layer chunks need four: [t0 t1 s0 s1])
-  int nw = max_nw;
-  size_t lds = 0;
-  bool fits = false;
-  const int ct_wish = a.ct_tiles;
-  for (; nw >= 1; --nw) {
-    for (int ct = ct_wish; ct >= 4 && !fits; ct = ct > 4 ? 4 : 0) {
-      lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
-            rt::bwd_lds_bytes(nw, a.ht_tiles, a.dt_tiles, ct);
-      if (lds <= 160 * 1024) {
+// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.
+static bool rnvp_bwd_rt_plan(int dim, int n_hidden, const int* hidden, RnvpBwdRtArgs& a, RtPlan& p) {
+  if (dim < 1 || n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || !hidden_ok(n_hidden, hidden)) return false;
+  int sizes[MNF_MAX_LINEAR + 1];
+  sizes[0] = dim;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  if (w.min < 4 || w.max > 128) return false;
+  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0);
+  const int hl = hidden[n_hidden - 1];
+  a.t_w = (int)off; off += (int64_t)hl * dim;
+  a.t_b = (int)off; off += dim;
+  a.s_w = (int)off; off += (int64_t)hl * dim;
+  a.s_b = (int)off; off += dim;
+  if (off >= (1ll << 31)) return false;
+  a.n_params = (int)off;
+  p.mt_max = w.max <= 64 ? 4 : 8;
+  const int MTh = (hl + 15) / 16, KSh = (16 * MTh + 31) / 32;
+  a.cb = 4 * KSh > 2 * MTh ? 4 * KSh : 2 * MTh;  // a round of the heads: 2 tiles x 2 heads x KSh blocks, then 2 x MTh turned ones
+  const int MT1 = (hidden[0] + 15) / 16;
+  if (a.cb < MT1) a.cb = MT1;  // (a K-step of the first layer)
+  if (a.cb < 8) a.cb = 8;
+  a.bt = p.mt_max > 4 ? p.mt_max : 4;
+  a.block_words = 2 * a.cb * rt::kBlockWords;
+  a.bias_words = 2 * a.bt * 16;
+  a.ht_tiles = w.tiles;
+  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
+  // rows per workgroup first (any wave count), then as many first-layer input tiles per chunk as still fit (the
+  // output-layer chunks need four: [t0 t1 s0 s1])
+  const int KS1 = (16 * MT1 + 31) / 32;
+  int ci = a.cb / KS1;
+  ci = ci > p.mt_max ? p.mt_max : ci < 4 ? 4 : ci;
+  for (p.nw = 8; p.nw >= 1; --p.nw) {
+    for (int ct = ci; ct >= 4; ct = ct > 4 ? 4 : 0) {
+      p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
+              rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, ct);
+      if (p.lds <= 160 * 1024) {
         a.ct_tiles = ct;
-        fits = true;
+        return true;
       }
     }
-    if (fits) break;
   }
-  if (nw < 1) return MNF_ERR_UNSUPPORTED;
-  auto kernel = rnvp_bwd_rt_kernel<MT_MAX>;
-  static DeviceMemo attr;
-  attr.get([&](int) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rnvp_bwd_rt_kernel<MT_MAX>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    return 1;
-  });
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t need = (a.rows + 16 * nw - 1) / (16 * nw);
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  tag_kernel("rnvp_bwd_rt");
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
-  return check_launch();
+  return false;
 }
 
 }  // namespace mnf
 
 using namespace mnf;
+
+extern "C" int mnf_rnvp_bwd_rt_supported(int dim, int n_hidden, const int* hidden) {
+  RnvpBwdRtArgs a;
+  RtPlan p;
+  return rnvp_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+}
 
 extern "C" int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
                                float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows,
@@ -232,48 +245,16 @@ extern "C" int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed,
   if (!z || !grad_z || !flat || !grad_scale_dev || rows < 0 || dim < 1 || n_hidden < 1 || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (n_hidden > rt::kMaxBwdLayers || deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  if (deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   RnvpBwdRtArgs a;
   memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!rnvp_bwd_rt_plan(dim, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
   a.z = z; a.mask = mask; a.seed = seed; a.grad_x = grad_x; a.grad_ld = grad_ld; a.grad_z = grad_z; a.grad_flat = grad_flat;
   a.flat = flat; a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim;
-  int sizes[MNF_MAX_LINEAR + 1];
-  sizes[0] = dim;
-  int mn = 1 << 30, mxh = 0, ht = 0, dt = 0;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-    mxh = hidden[i] > mxh ? hidden[i] : mxh;
-    ht += (hidden[i] + 15) / 16;
-    dt = (hidden[i] + 15) / 16 > dt ? (hidden[i] + 15) / 16 : dt;
-  }
-  if (mn < 4 || mxh > 128) return MNF_ERR_UNSUPPORTED;
-  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0);
-  const int hl = hidden[n_hidden - 1];
-  a.t_w = (int)off; off += (int64_t)hl * dim;
-  a.t_b = (int)off; off += dim;
-  a.s_w = (int)off; off += (int64_t)hl * dim;
-  a.s_b = (int)off; off += dim;
-  if (off >= (1ll << 31)) return MNF_ERR_UNSUPPORTED;
-  a.n_params = (int)off;
-  auto aligned = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  a.vec = dim % 4 == 0 && aligned(z) && aligned(grad_z) && (!mask || aligned(mask)) && (!grad_x || aligned(grad_x));
-  const int MT_MAX = mxh <= 64 ? 4 : 8;
-  const int MTh = (hl + 15) / 16, KSh = (16 * MTh + 31) / 32;
-  a.cb = 4 * KSh > 2 * MTh ? 4 * KSh : 2 * MTh;  // a round of the heads: 2 tiles x 2 heads x KSh blocks, then 2 x MTh turned ones
-  const int MT1 = (hidden[0] + 15) / 16;
-  if (a.cb < MT1) a.cb = MT1;  // (a K-step of the first layer)
-  if (a.cb < 8) a.cb = 8;
-  a.bt = MT_MAX > 4 ? MT_MAX : 4;
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
-  a.ht_tiles = ht;
-  a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
-  (void)dt;
-  const int KS1 = (16 * MT1 + 31) / 32;
-  int ci = a.cb / KS1;
-  ci = ci > MT_MAX ? MT_MAX : ci;
-  a.ct_tiles = ci < 4 ? 4 : ci;  // (the wish: rnvp_bwd_rt_launch_class settles for four where that buys a larger workgroup)
-  if (MT_MAX == 4) return rnvp_bwd_rt_launch_class<4>(a, 8, (hipStream_t)stream);
-  return rnvp_bwd_rt_launch_class<8>(a, 8, (hipStream_t)stream);
+  a.vec = dim % 4 == 0 && aligned16(z, grad_z, mask, grad_x);
+  static DeviceMemo attr;
+  allow_big_lds(attr, rnvp_bwd_rt_kernel<4>, rnvp_bwd_rt_kernel<8>);
+  auto kernel = p.mt_max == 4 ? rnvp_bwd_rt_kernel<4> : rnvp_bwd_rt_kernel<8>;
+  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "rnvp_bwd_rt", (hipStream_t)stream);
 }

@@ -147,79 +147,23 @@ __global__ void __launch_bounds__(NW * 64) rnvp_rt_kernel(RnvpRtArgs a) {
   }
 }
 
-template <typename K>
-static void rnvp_rt_allow_big_lds(K kernel) {
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <int MT_MAX, int NW>
-static int rnvp_rt_launch_class(RnvpRtArgs& a, int64_t n_blocks, int64_t n_bias, int cb_stream, hipStream_t stream) {
-  constexpr int kResidentBytes = 150 * 1024;
-  // Rows that are not 16-byte aligned (dim not a multiple of 4, a view at an odd offset) have the resident variant only,
-  // except in the widest class, whose streaming kernel takes the alignment at run time (a branch around every row access:
-  // 15-20 % on the memory-bound shapes) and serves every width: rnvp_rt_launch sends such a call there.
-  const bool resident = n_blocks * 2048 + n_bias * 64 <= kResidentBytes;
-  constexpr int kStreamVec = MT_MAX == 16 ? 2 : 1;
-  if (!resident && !a.vec && kStreamVec != 2) return MNF_ERR_UNSUPPORTED;
-  if (resident) {
-    a.cb = (int)n_blocks;
-    a.bt = (int)n_bias;
-    a.block_words = (int)n_blocks * rt::kBlockWords;
-    a.bias_words = (int)n_bias * 16;
-  } else {
-    a.cb = cb_stream;
-    a.bt = cb_stream;
-    a.block_words = 2 * cb_stream * rt::kBlockWords;
-    a.bias_words = 2 * cb_stream * 16;
-  }
-  const size_t lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
-  static DeviceMemo attr;
-  attr.get([&](int) {
-    rnvp_rt_allow_big_lds(rnvp_rt_kernel<MT_MAX, NW, true, 1>);
-    rnvp_rt_allow_big_lds(rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>);
-    rnvp_rt_allow_big_lds(rnvp_rt_kernel<MT_MAX, NW, true, 0>);
-    return 1;
-  });
-  auto kernel = !resident ? rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>
-                          : a.vec ? rnvp_rt_kernel<MT_MAX, NW, true, 1> : rnvp_rt_kernel<MT_MAX, NW, true, 0>;
-  const int nw = NW == 8 && resident && lds <= 79 * 1024 ? 4 : NW;  // (streaming: every wave of the CU shares one conversion of the weights)
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t rows_per_block = (int64_t)nw * 16;
-  const int64_t need = (a.rows + rows_per_block - 1) / rows_per_block;
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
-  return check_launch();
-}
-
-// MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
-int rnvp_rt_launch(const float* z, const float* mask, uint64_t seed, float* x, float* log_det, int accumulate,
-                   const float* flat, int64_t rows, int dim, int n_hidden, const int* hidden, hipStream_t stream) {
-  if (!flat || n_hidden < 1 || n_hidden > MNF_MAX_LINEAR || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
-  RnvpRtArgs a;
-  memset(&a, 0, sizeof(a));
-  a.z = z; a.mask = mask; a.seed = seed; a.x = x; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim;
-  a.accumulate = accumulate != 0;
+// The launch of a shape (`aligned`: z, x and the mask 16-byte aligned), or false: the VALU kernel takes it.  Fills the
+// kernel arguments' shape part.
+static bool rnvp_rt_plan(int dim, int n_hidden, const int* hidden, bool aligned, RnvpRtArgs& a, RtPlan& p) {
+  if (dim < 1 || n_hidden < 1 || !hidden_ok(n_hidden, hidden)) return false;
   int sizes[MNF_MAX_LINEAR + 1];
   sizes[0] = dim;
-  int mn = 1 << 30, mxh = 0;
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    mn = hidden[i] < mn ? hidden[i] : mn;
-    mxh = hidden[i] > mxh ? hidden[i] : mxh;
-  }
-  if (mn < 4 || mxh > 256) return MNF_ERR_UNSUPPORTED;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  if (w.min < 4 || w.max > 256) return false;
   int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0);
   const int hl = hidden[n_hidden - 1];
   a.t_w = (int)off; off += (int64_t)hl * dim;
   a.t_b = (int)off; off += dim;
   a.s_w = (int)off; off += (int64_t)hl * dim;
   a.s_b = (int)off; off += dim;
-  if (off >= (1ll << 31)) return MNF_ERR_UNSUPPORTED;
+  if (off >= (1ll << 31)) return false;
   a.n_params = (int)off;
-  a.vec = dim % 4 == 0 && (reinterpret_cast<uintptr_t>(z) & 15) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                   (!mask || (reinterpret_cast<uintptr_t>(mask) & 15) == 0);
+  a.vec = dim % 4 == 0 && aligned;
   int64_t n_blocks = 0, n_bias = 0;
   for (int l = 0; l < n_hidden; ++l) {
     const int in_cols = l == 0 ? dim : 16 * ((sizes[l] + 15) / 16);
@@ -229,12 +173,52 @@ int rnvp_rt_launch(const float* z, const float* mask, uint64_t seed, float* x, f
   const int KS = (16 * ((hl + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
   n_blocks += 2ll * KS * M;
   n_bias += 2ll * M;
-  tag_kernel("rnvp_rt");
-  int rc = MNF_ERR_UNSUPPORTED;
-  if (mxh <= 64) rc = rnvp_rt_launch_class<4, 8>(a, n_blocks, n_bias, 16, stream);
-  else if (mxh <= 128) rc = rnvp_rt_launch_class<8, 8>(a, n_blocks, n_bias, 16, stream);
-  if (rc == MNF_ERR_UNSUPPORTED) rc = rnvp_rt_launch_class<16, 4>(a, n_blocks, n_bias, 16, stream);
-  return rc;
+  // Rows that are not 16-byte aligned (dim not a multiple of 4, a view at an odd offset) have the resident variant only,
+  // except in the widest class, whose streaming kernel takes the alignment at run time (a branch around every row access:
+  // 15-20 % on the memory-bound shapes) and serves every width: such a call goes there.
+  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
+  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
+  p.mt_max = !p.resident && !a.vec ? 16 : w.max <= 64 ? 4 : w.max <= 128 ? 8 : 16;
+  a.cb = p.resident ? (int)n_blocks : kStream;
+  a.bt = p.resident ? (int)n_bias : kStream;
+  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
+  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
+  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
+  // (streaming: every wave of the CU shares one conversion of the weights)
+  p.nw = p.mt_max == 16 || (p.resident && p.lds <= 79 * 1024) ? 4 : 8;
+  return true;
+}
+
+template <int MT_MAX, int NW>
+static int rnvp_rt_launch_class(const RnvpRtArgs& a, const RtPlan& p, hipStream_t stream) {
+  constexpr int kStreamVec = MT_MAX == 16 ? 2 : 1;
+  static DeviceMemo attr;
+  allow_big_lds(attr, rnvp_rt_kernel<MT_MAX, NW, true, 1>, rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>,
+                rnvp_rt_kernel<MT_MAX, NW, true, 0>);
+  auto kernel = !p.resident ? rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>
+                            : a.vec ? rnvp_rt_kernel<MT_MAX, NW, true, 1> : rnvp_rt_kernel<MT_MAX, NW, true, 0>;
+  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, "rnvp_rt", stream);
+}
+
+// MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
+int rnvp_rt_launch(const float* z, const float* mask, uint64_t seed, float* x, float* log_det, int accumulate,
+                   const float* flat, int64_t rows, int dim, int n_hidden, const int* hidden, hipStream_t stream) {
+  if (!flat || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  RnvpRtArgs a;
+  memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!rnvp_rt_plan(dim, n_hidden, hidden, aligned16(z, x, mask), a, p)) return MNF_ERR_UNSUPPORTED;
+  a.z = z; a.mask = mask; a.seed = seed; a.x = x; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim;
+  a.accumulate = accumulate != 0;
+  if (p.mt_max == 4) return rnvp_rt_launch_class<4, 8>(a, p, stream);
+  if (p.mt_max == 8) return rnvp_rt_launch_class<8, 8>(a, p, stream);
+  return rnvp_rt_launch_class<16, 4>(a, p, stream);
 }
 
 }  // namespace mnf
+
+extern "C" int mnf_rnvp_rt_supported(int dim, int n_hidden, const int* hidden) {
+  mnf::RnvpRtArgs a;
+  mnf::RtPlan p;
+  return mnf::rnvp_rt_plan(dim, n_hidden, hidden, true, a, p) ? 1 : 0;
+}

@@ -341,8 +341,8 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
             rc = lib.mnf_affine_half_bwd_mfma(
                 x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, index.data_ptr(), rows,
                 f.dim, int(bool(f.parity)), int(inverse), *hid, _stream())
-    if rc == _lib.MNF_ERR_UNSUPPORTED and flat_ptr is not None and f.force_generic != 1 \
-            and (f.force_generic == 2 or (rows >= _dispatch.RT_MIN_ROWS and not f._fp32_request())) and (y_out is not None or not inverse or not f.scale):
+    if rc == _lib.MNF_ERR_UNSUPPORTED and flat_ptr is not None and (y_out is not None or not inverse or not f.scale) \
+            and _dispatch.wants_rt(rows, f.force_generic, f._fp32_request()):
         # no per-shape gradient kernel: the run-time-shaped matrix-core one (any 1..4 hidden layers of widths 4..64)
         sc = scale if scale is not None else _grad_scale(gy, gl, rows, f.dim, x_in.device)
         rc = lib.mnf_affine_half_bwd_rt(
@@ -467,8 +467,7 @@ class _NsfFn(torch.autograd.Function):
                     x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), *args,
                     cold.data_ptr(), cap, _stream()))
                 return grad_x, grad_flat, None, None
-        if m.force_generic != 1 and _dispatch.NSF_BWD_KERNEL != "generic" and (
-                m.force_generic == 2 or (rows >= _dispatch.RT_MIN_ROWS and not m._fp32_request())):
+        if _dispatch.NSF_BWD_KERNEL != "generic" and _dispatch.wants_rt(rows, m.force_generic, m._fp32_request()):
             # no per-shape gradient kernel: the run-time-shaped matrix-core one (any dim, K <= 16, hidden widths 4..64)
             scale = _grad_scale(gy, gl, rows, m.dim, x.device)
             rc = lib.mnf_nsf_cl_bwd_rt(
@@ -573,8 +572,7 @@ class _RnvpFn(torch.autograd.Function):
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_rnvp_bwd_mfma", rc)
                 return grad_z, ret_flat, None, None, None, None
-        if m.force_generic != 1 and not _dispatch.RNVP_BWD_GENERIC and (
-                m.force_generic == 2 or (z.shape[0] >= _dispatch.RT_MIN_ROWS and not m._fp32_request())):
+        if not _dispatch.RNVP_BWD_GENERIC and _dispatch.wants_rt(z.shape[0], m.force_generic, m._fp32_request()):
             # no per-shape gradient kernel: the run-time-shaped matrix-core one (1..4 conditioner layers of widths 4..128)
             scale = _grad_scale(gx, gl, z.shape[0], m.dim, z.device)
             rc = lib.mnf_rnvp_bwd_rt(
