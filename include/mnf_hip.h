@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 15
+#define MNF_ABI_VERSION 16
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -86,8 +86,11 @@ const char* mnf_last_kernel(void);
  * device -- in place, also where this header passes it as const -- and run as ONE workgroup, so that their sums follow
  * the list (slow; such rows are the exception).  tools/soak_determinism_train.py: 0 differing tensors with a tenth of
  * the rows forced onto those passes.  The run-time-shaped gradient kernels (mnf_*_bwd_rt) return MNF_ERR_UNSUPPORTED
- * under the switch: their shapes then take the VALU gradient kernels, which add atomically across workgroups -- the
- * switch covers the shapes with per-shape gradient kernels (the reference's configurations), not every shape. */
+ * under the switch; their mnf_*_bwd_rt_det forms (any mode) give every workgroup a slot of its own in a workspace and add
+ * the slots up in order, and the Python layer takes them for those shapes.  Not covered: the VALU any-shape gradient
+ * kernels (*_bwd_generic: shapes outside every matrix-core gradient kernel, and batches below 2,048 rows that no per-shape
+ * kernel takes) add atomically across workgroups in either mode; the Python layer warns once per layer and shape when a
+ * gradient pass lands there under the switch. */
 int mnf_deterministic(void);
 /* Number of visible devices whose gcnArchName starts with gfx950 (0 = none / no driver). */
 int mnf_device_count(void);
@@ -590,6 +593,21 @@ int mnf_affine_half_bwd_rt(const float* x, const float* y, const float* grad_y, 
                            float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
                            int parity, int inverse, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
                            void* stream);
+/* The run-time-shaped gradient launches with FIXED-ORDER parameter sums, in either mode (the Python layer takes them under
+ * MNF_DETERMINISTIC=1): the same kernel, each workgroup of its persistent grid adding into a slot of its own in
+ * `workspace` (one lane per parameter entry, in program order), then one launch adding the slots to grad_flat in slot
+ * order -- grad_flat is ADDED to, as by the atomic form.  The *_det_workspace queries give the floats `workspace` must hold
+ * for `rows` rows (the grid, capped so that the slots stay within 512 MiB, times the parameter count rounded up to 64); 0
+ * where the *_bwd_rt_supported query refuses the shape or no gfx950 device is visible.  MNF_ERR_INVALID_ARG, before any
+ * launch: a NULL pointer the atomic form also refuses, or a non-empty batch with grad_flat != NULL and a NULL workspace or
+ * fewer floats than the query gives (grad_flat == NULL: no parameter sums, workspace unused).  The launches keep their
+ * kernel family names (ahf_bwd_rt, nsf_bwd_rt, rnvp_bwd_rt). */
+int64_t mnf_affine_half_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host, int has_scale,
+                                             int has_shift);
+int mnf_affine_half_bwd_rt_det(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                               float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                               int parity, int inverse, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                               float* workspace, int64_t workspace_floats, void* stream);
 int mnf_nsf_cl_bwd(const float* x, const float* grad_y, const float* grad_ld, float* grad_x,
                    float* grad_flat, const float* flat, int64_t rows, int dim, int K, float tail_bound,
                    int inverse, int n_hidden, const int* hidden_host, void* stream);
@@ -633,6 +651,12 @@ int mnf_nsf_cl_bwd_tile_fixup(const float* x, const float* grad_y, const float* 
 int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
                       float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
                       float tail_bound, int inverse, int n_hidden, const int* hidden_host, void* stream);
+/* Fixed-order sums: as mnf_affine_half_bwd_rt_det. */
+int64_t mnf_nsf_cl_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_nsf_cl_bwd_rt_det(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                          float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
+                          float tail_bound, int inverse, int n_hidden, const int* hidden_host, float* workspace,
+                          int64_t workspace_floats, void* stream);
 /* mask == NULL: the mask of the seeded forward call is regenerated from `seed`. */
 int mnf_rnvp_bwd(const float* z, const float* mask, uint64_t seed, const float* grad_x,
                  const float* grad_ld, float* grad_z, float* grad_flat, const float* flat,
@@ -679,12 +703,17 @@ int mnf_rnvp_bwd_mfma_phases(const float* z, const float* mask, uint64_t seed, c
 int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld, float* grad_z,
                     float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int n_hidden,
                     const int* hidden_host, void* stream);
+/* Fixed-order sums: as mnf_affine_half_bwd_rt_det. */
+int64_t mnf_rnvp_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host);
+int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
+                        float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                        int n_hidden, const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
 /* Shape queries of the run-time-shaped kernels, host only (no GPU needed): 1 where the kernel has a launch for the shape,
  * 0 where its entry point -- mnf_affine_half / mnf_nsf_cl / mnf_rnvp* for the forward kernels, which then run the VALU
  * kernel -- refuses it; the launchers answer from the same plan.  Not covered: the row count (with force_generic == 0 the
  * forward entry points take the kernel from 2,048 rows on; torch_mnf_amd/_dispatch.py decides it for the gradients), the
  * alignment of the rows (unaligned ones take another variant, never a refusal) and MNF_DETERMINISTIC (the *_bwd_rt
- * kernels then refuse every shape).  The limits:
+ * entries then refuse every shape; their *_bwd_rt_det forms take the same shapes).  The limits:
  *   mnf_affine_half_rt_supported      >= 1 hidden layer, widths 4 .. 256, any even dim
  *   mnf_affine_half_bwd_rt_supported  1 .. 4 hidden layers of widths 4 .. 64, any even dim
  *   mnf_nsf_cl_rt_supported           K = 2 .. 16, >= 1 hidden layer, widths 4 .. 64, any even dim

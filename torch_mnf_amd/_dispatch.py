@@ -40,8 +40,10 @@ layer, K <= 8 takes n_h <= 64; K = 9 n_h <= 64 at 1-2 layers, 48 at 3-4; K = 10.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and
-RNVP: wherever a split kernel exists; NSF_CL: the K = 8 shapes, plain layer only), else the VALU kernel; and under
-MNF_DETERMINISTIC=1 the *_bwd_rt kernels (atomic sums) refuse, so their shapes take the VALU gradient kernels.
+RNVP: wherever a split kernel exists; NSF_CL: the K = 8 shapes, plain layer only), else the VALU kernel.  Under
+MNF_DETERMINISTIC=1 the *_bwd_rt shapes run the same kernels in their fixed-order form (mnf_*_bwd_rt_det: a slot per
+workgroup, added up in order; same kernel family names, same tiers); the VALU gradient kernels stay atomic and warn once
+per layer and shape (_lib.note_atomic_sums).
 layer.force_generic = 1 / 2 forces the VALU / the run-time-shaped kernels (tests, tools/coverage_map.py).
 """
 
@@ -100,7 +102,7 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
-    """Tier of one layer call in default mode (no force_generic, no fp32 request, no MNF_DETERMINISTIC): kind "ahf" |
+    """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
     "nsf" | "rnvp", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3)."""
     from . import _lib
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 15  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 16  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -103,10 +103,17 @@ SIGNATURES = {
                                              c_void_p, c_int64, c_void_p]),
     "mnf_affine_half_bwd_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int, c_int, c_int, c_int, _intp, c_int, c_int, c_void_p]),
+    "mnf_affine_half_bwd_rt_det_workspace": (c_int64, [c_int64, c_int, c_int, _intp, c_int, c_int]),
+    "mnf_affine_half_bwd_rt_det": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_int64, c_int, c_int, c_int, c_int, _intp, c_int, c_int, c_void_p, c_int64,
+                                           c_void_p]),
     "mnf_nsf_cl_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                c_float, c_int, c_int, _intp, c_void_p]),
     "mnf_nsf_cl_bwd_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                   c_int, c_int, c_float, c_int, c_int, _intp, c_void_p]),
+    "mnf_nsf_cl_bwd_rt_det_workspace": (c_int64, [c_int64, c_int, c_int, c_int, _intp]),
+    "mnf_nsf_cl_bwd_rt_det": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int, c_int, c_float, c_int, c_int, _intp, c_void_p, c_int64, c_void_p]),
     "mnf_nsf_cl_bwd_tile_supported": (c_int, [c_int, c_int, c_int, _intp]),
     "mnf_nsf_cl_bwd_tile_layout": (c_int, [c_int, c_int, c_int, _intp, _i64p, _i64p, _i64p]),
     "mnf_nsf_cl_bwd_tile_index": (c_int, [c_int, c_int, c_int, _intp, _i32p, _i32p]),
@@ -120,6 +127,9 @@ SIGNATURES = {
                              c_int64, c_int, c_int, _intp, c_void_p]),
     "mnf_rnvp_bwd_rt": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_int, c_int, _intp, c_void_p]),
+    "mnf_rnvp_bwd_rt_det_workspace": (c_int64, [c_int64, c_int, c_int, _intp]),
+    "mnf_rnvp_bwd_rt_det": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_int64, c_int, c_int, _intp, c_void_p, c_int64, c_void_p]),
     "mnf_affine_half_rt_supported": (c_int, [c_int, c_int, _intp, c_int, c_int]),
     "mnf_affine_half_bwd_rt_supported": (c_int, [c_int, c_int, _intp, c_int, c_int]),
     "mnf_nsf_cl_rt_supported": (c_int, [c_int, c_int, c_int, _intp]),
@@ -289,4 +299,25 @@ def note_generic(layer: str, rows: int, shape: str) -> None:
     import warnings
     warnings.warn(f"torch_mnf_amd: {layer}({shape}) ran on the any-shape kernel {name!r} at {rows} rows: no matrix-core "
                   "kernel for this shape (see INTEGRATION.md, 'Which kernel runs'); results are the same, the speed is not",
+                  RuntimeWarning, stacklevel=3)
+
+
+_WARNED_ATOMIC: set = set()
+
+
+def note_atomic_sums(layer: str, shape: str) -> None:
+    """Under MNF_DETERMINISTIC=1, once per (layer, shape) and at any row count: tell the caller that a gradient pass just
+    ran on an any-shape VALU kernel ("*_generic"), which adds its parameter sums with float atomics across workgroups --
+    they can differ in their last bits from run to run, which the switch asks not to happen.  The matrix-core gradient
+    kernels all have fixed-order forms (include/mnf_hip.h mnf_deterministic); this is where the guarantee stops."""
+    if not deterministic() or (layer, shape) in _WARNED_ATOMIC:
+        return
+    name = last_kernel()
+    if "generic" not in name:
+        return
+    _WARNED_ATOMIC.add((layer, shape))
+    import warnings
+    warnings.warn(f"torch_mnf_amd: {layer}({shape}) ran on {name!r} under MNF_DETERMINISTIC=1: this kernel adds its "
+                  "parameter gradients atomically across workgroups, so they may differ in their last bits from run to "
+                  "run (no fixed-order gradient kernel for this shape and row count; see INTEGRATION.md 3c)",
                   RuntimeWarning, stacklevel=3)

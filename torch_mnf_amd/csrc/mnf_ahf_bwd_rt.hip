@@ -34,6 +34,7 @@ struct AhfBwdRtArgs {
   int cb, bt, block_words, bias_words;  // weight stream (mnf_rt.h Source<false>)
   int ht_tiles, dt_tiles, ct_tiles;     // exchange tiles: hidden vectors of one net | one layer's deltas | a chunk
   NetDesc s_net, t_net;
+  int64_t slot_floats;  // 0; mnf_affine_half_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
 };
 
 constexpr float kLog2eB = 1.4426950408889634f;
@@ -64,6 +65,7 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
   const int cond_off = a.parity ? H : 0, act_off = a.parity ? 0 : H;
   const int n_nets = (a.has_scale ? 1 : 0) + (a.has_shift ? 1 : 0);
   const int64_t n_blocks = (a.rows + 16 * nw - 1) / (16 * nw);
+  float* const gflat = a.grad_flat + blockIdx.x * a.slot_floats;
 
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
     const int64_t r = blk * (16 * nw) + 16 * wave + j;
@@ -81,7 +83,6 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
       const bool is_s = a.has_scale && pass == 0;
       const NetDesc& nd = is_s ? a.s_net : a.t_net;
       const int n_hid = nd.n_lin - 1, L = n_hid;
-      float* gflat = a.grad_flat;
       // ---- forward recompute: every hidden vector goes, turned, into the exchange area; its sign bits into LDS
       Hidden<MT_MAX, 1> h;
       {
@@ -248,14 +249,28 @@ extern "C" int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int
   return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p) ? 1 : 0;
 }
 
-extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
-                                      float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
-                                      int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
-                                      void* stream) {
+static DeviceMemo ahf_bwd_rt_attr;
+
+extern "C" int64_t mnf_affine_half_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden, int has_scale,
+                                                        int has_shift) {
+  AhfBwdRtArgs a;
+  RtPlan p;
+  if (rows < 1 || rows * dim >= (1ll << 40) || !ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p)) return 0;
+  if (!gfx950_visible()) return 0;
+  allow_big_lds(ahf_bwd_rt_attr, ahf_bwd_rt_kernel<4>);
+  return rt_det_workspace(ahf_bwd_rt_kernel<4>, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params);
+}
+
+// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+static int ahf_bwd_rt_run(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                          float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int parity,
+                          int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift, bool det,
+                          float* workspace, int64_t workspace_floats, void* stream) {
   if (!x || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
+  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if ((inverse && has_scale && !y) || deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  if ((inverse && has_scale && !y) || (!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   AhfBwdRtArgs a;
   memset(&a, 0, sizeof(a));
   RtPlan p;
@@ -264,7 +279,24 @@ extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const floa
   a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity != 0; a.inverse = inverse != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
   a.vec = dim % 8 == 0 && aligned16(x, grad_x, y, grad_y);
-  static DeviceMemo attr;
-  allow_big_lds(attr, ahf_bwd_rt_kernel<4>);
-  return launch_persistent(ahf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "ahf_bwd_rt", (hipStream_t)stream);
+  allow_big_lds(ahf_bwd_rt_attr, ahf_bwd_rt_kernel<4>);
+  return launch_rt_bwd(ahf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params, det, workspace,
+                       workspace_floats, "ahf_bwd_rt", (hipStream_t)stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                                      float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                                      int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
+                                      void* stream) {
+  return ahf_bwd_rt_run(x, y, grad_y, grad_ld, grad_x, grad_flat, flat, grad_scale_dev, rows, dim, parity, inverse, n_hidden,
+                        hidden, has_scale, has_shift, false, nullptr, 0, stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt_det(const float* x, const float* y, const float* grad_y, const float* grad_ld,
+                                          float* grad_x, float* grad_flat, const float* flat, const float* grad_scale_dev,
+                                          int64_t rows, int dim, int parity, int inverse, int n_hidden, const int* hidden,
+                                          int has_scale, int has_shift, float* workspace, int64_t workspace_floats,
+                                          void* stream) {
+  return ahf_bwd_rt_run(x, y, grad_y, grad_ld, grad_x, grad_flat, flat, grad_scale_dev, rows, dim, parity, inverse, n_hidden,
+                        hidden, has_scale, has_shift, true, workspace, workspace_floats, stream);
 }

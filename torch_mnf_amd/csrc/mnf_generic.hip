@@ -801,6 +801,10 @@ bool deterministic() {
   }();
   return on;
 }
+bool gfx950_visible() {
+  static const bool on = mnf_device_count() > 0;
+  return on;
+}
 
 __global__ void __launch_bounds__(256) zero_floats_kernel(float* __restrict__ p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 0.f;

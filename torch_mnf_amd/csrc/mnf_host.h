@@ -141,15 +141,20 @@ inline void allow_big_lds(DeviceMemo& memo, K... kernels) {
   });
 }
 // persistent grid: as many workgroups of nw waves as the occupancy query says are resident (one per CU if it fails), at
-// most one per `rows_per_block` rows; tags the launch with the kernel family `tag`
+// most one per `rows_per_block` rows
 template <typename Args>
-inline int launch_persistent(void (*kernel)(Args), const Args& a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
-                             const char* tag, hipStream_t stream) {
+inline int64_t persistent_grid(void (*kernel)(Args), int nw, size_t lds, int64_t rows_per_block, int64_t rows) {
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
   const int64_t need = (rows + rows_per_block - 1) / rows_per_block;
-  int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  if (grid > need) grid = need;
+  const int64_t grid = (int64_t)per_cu * device_cus(current_device());
+  return grid > need ? need : grid;
+}
+// ... launched; tags the launch with the kernel family `tag`
+template <typename Args>
+inline int launch_persistent(void (*kernel)(Args), const Args& a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
+                             const char* tag, hipStream_t stream) {
+  const int64_t grid = persistent_grid(kernel, nw, lds, rows_per_block, rows);
   tag_kernel(tag);
   hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
   return check_launch();
@@ -218,6 +223,47 @@ bool deterministic();
 // n floats := 0 / dst[i] += part[0][i] + part[1][i] + ... (rows in order, row r at part + r * stride), as kernel nodes
 int zero_floats_async(float* p, int64_t n, hipStream_t stream);
 int det_reduce_async(const float* part, int n_rows, int64_t stride, int64_t count, float* dst, hipStream_t stream);
+
+// The fixed-order form of the run-time-shaped gradient launches (mnf_*_bwd_rt_det): every workgroup of the persistent
+// grid adds into a slot of its own (grad_flat + blockIdx.x * slot_floats), and det_reduce_async adds the slots up in
+// order.  A parameter's entry in a slot receives its adds from ONE lane, in program order (the weight-gradient products
+// go to the waves by shape alone, mnf_rt_bwd.h dw_phase_rows), so that every slot -- and the sum -- is the same every
+// run.  The grid is persistent_grid's, capped so that the slots stay within kRtDetMaxBytes.
+constexpr int64_t kRtDetMaxBytes = (int64_t)512 << 20;
+inline int64_t rt_det_slot_floats(int64_t n_params) { return (n_params + 63) / 64 * 64; }  // whole 256-byte lines
+inline int64_t rt_det_slots(int64_t grid, int64_t n_params) {
+  int64_t cap = kRtDetMaxBytes / (4 * rt_det_slot_floats(n_params));
+  if (cap < 1) cap = 1;
+  return grid < cap ? grid : cap;
+}
+bool gfx950_visible();  // mnf_device_count() > 0, asked once per process
+// det: the slots in `workspace` (at least slots x slot_floats floats, else MNF_ERR_INVALID_ARG before any launch), zeroed,
+// filled, added to a.grad_flat; grad_flat == NULL or !det: launch_persistent
+template <typename Args>
+inline int launch_rt_bwd(void (*kernel)(Args), Args a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
+                         int64_t n_params, bool det, float* workspace, int64_t workspace_floats, const char* tag,
+                         hipStream_t stream) {
+  a.slot_floats = 0;
+  if (!det || !a.grad_flat) return launch_persistent(kernel, a, nw, lds, rows_per_block, rows, tag, stream);
+  const int64_t slots = rt_det_slots(persistent_grid(kernel, nw, lds, rows_per_block, rows), n_params);
+  const int64_t slot = rt_det_slot_floats(n_params);
+  if (!workspace || workspace_floats < slots * slot) return MNF_ERR_INVALID_ARG;
+  float* const dst = a.grad_flat;
+  a.grad_flat = workspace;
+  a.slot_floats = slot;
+  int rc = zero_floats_async(workspace, slots * slot, stream);
+  if (rc != MNF_OK) return rc;
+  tag_kernel(tag);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)slots), dim3(nw * 64), lds, stream, a);
+  rc = check_launch();
+  return rc != MNF_OK ? rc : det_reduce_async(workspace, (int)slots, slot, n_params, dst, stream);
+}
+// floats of workspace launch_rt_bwd's det form needs (0: no gfx950 device visible)
+template <typename K>
+inline int64_t rt_det_workspace(K kernel, int nw, size_t lds, int64_t rows_per_block, int64_t rows, int64_t n_params) {
+  if (rows < 1 || !gfx950_visible()) return 0;
+  return rt_det_slots(persistent_grid(kernel, nw, lds, rows_per_block, rows), n_params) * rt_det_slot_floats(n_params);
+}
 // The fp32 fix-up passes under MNF_DETERMINISTIC: the matrix-core gradient launches hand back the tiles / row groups
 // whose operands left the split range as a LIST filled through an atomic counter -- the same ids every run, in any order.
 // det_sort_ids_async sorts ids[0 .. min(*count, capacity)) (distinct values in [0, n_items)) ascending, in place, as a

@@ -39,6 +39,7 @@ struct NsfBwdRtArgs {
   int cb, bt, block_words, bias_words;
   int ht_tiles, dt_tiles, ct_tiles;
   NetDesc f1, f2;
+  int64_t slot_floats;  // 0; mnf_nsf_cl_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
 };
 
 // the tv-th parameter tile of a slot (widths | heights | derivatives, four positions per tile) -> first position 16 c + k0
@@ -103,7 +104,7 @@ template <int MT_MAX, int K, typename Src>
 __device__ __forceinline__ void nsf_bwd_slots(const NsfBwdRtArgs& a, Src& src, const NetDesc& nd, const rt::BwdLds& lds, float wup,
                                               float gs, float inv_gs, const rt::Hidden<MT_MAX, 1>& h, const float* xrow,
                                               const float* gorow, float* gxrow, int act_off, bool live, float gl,
-                                              rt::Acc<MT_MAX, 1>& accd, float& downd) {
+                                              float* gflat, rt::Acc<MT_MAX, 1>& accd, float& downd) {
   using namespace rt;
   const bool VEC = a.vec != 0;  // (uniform)
   constexpr int NW_ = (K + 3) / 4, ND_ = (K - 1 + 3) / 4, TV = 2 * NW_ + ND_, KSO = (TV + 1) / 2;
@@ -113,7 +114,6 @@ __device__ __forceinline__ void nsf_bwd_slots(const NsfBwdRtArgs& a, Src& src, c
   const int ht_last = exH_tile_of(nd, L);
   const float* W = a.flat + nd.w_off[L];
   const float* B = a.flat + nd.b_off[L];
-  float* gflat = a.grad_flat;
   const float rowmask = live ? 1.f : 0.f;
   f32x4 vin = f32x4{0.f, 0.f, 0.f, 0.f}, gin = vin, vout = vin;
 #pragma unroll 1
@@ -212,6 +212,7 @@ __global__ void __launch_bounds__(512) nsf_bwd_rt_kernel(NsfBwdRtArgs a) {
   const float gs = *a.gscale_dev, inv_gs = 1.f / gs;
   const int H = a.dim / 2;
   const int64_t n_blocks = (a.rows + 16 * nw - 1) / (16 * nw);
+  float* const gflat = a.grad_flat + blockIdx.x * a.slot_floats;
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
     const int64_t r = blk * (16 * nw) + 16 * wave + j;
     const bool live = r < a.rows;
@@ -244,7 +245,7 @@ __global__ void __launch_bounds__(512) nsf_bwd_rt_kernel(NsfBwdRtArgs a) {
       float downd = 1.f;
       switch (a.K) {  // (uniform)
 #define MNF_NSF_BWD_CASE(KK) \
-  case KK: nsf_bwd_slots<MT_MAX, KK>(a, src, nd, lds, wup, gs, inv_gs, h, xrow, gorow, gxrow, act_off, live, gl, accd, downd); break;
+  case KK: nsf_bwd_slots<MT_MAX, KK>(a, src, nd, lds, wup, gs, inv_gs, h, xrow, gorow, gxrow, act_off, live, gl, gflat, accd, downd); break;
         MNF_NSF_BWD_CASE(2) MNF_NSF_BWD_CASE(3) MNF_NSF_BWD_CASE(4) MNF_NSF_BWD_CASE(5) MNF_NSF_BWD_CASE(6) MNF_NSF_BWD_CASE(7)
         MNF_NSF_BWD_CASE(8) MNF_NSF_BWD_CASE(9) MNF_NSF_BWD_CASE(10) MNF_NSF_BWD_CASE(11) MNF_NSF_BWD_CASE(12)
         MNF_NSF_BWD_CASE(13) MNF_NSF_BWD_CASE(14) MNF_NSF_BWD_CASE(15) MNF_NSF_BWD_CASE(16)
@@ -260,7 +261,7 @@ __global__ void __launch_bounds__(512) nsf_bwd_rt_kernel(NsfBwdRtArgs a) {
                                       : load4(gxrow + cond_off, col, H, VEC);
         store4(gxrow + cond_off, col, H, VEC, live, base + g);
       };
-      backward_tail<MT_MAX>(src, a.flat, a.grad_flat, nd, n_hid, -1, dv, lds, wup, inv_gs, H, load_in, add_in);
+      backward_tail<MT_MAX>(src, a.flat, gflat, nd, n_hid, -1, dv, lds, wup, inv_gs, H, load_in, add_in);
     }
   }
 }
@@ -307,15 +308,28 @@ extern "C" int mnf_nsf_cl_bwd_rt_supported(int dim, int K, int n_hidden, const i
   return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
 }
 
-extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
-                                 float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
-                                 float tail_bound, int inverse, int n_hidden, const int* hidden, void* stream) {
+static DeviceMemo nsf_bwd_rt_attr;
+
+extern "C" int64_t mnf_nsf_cl_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
+  NsfBwdRtArgs a;
+  RtPlan p;
+  if (rows < 1 || rows * dim >= (1ll << 40) || !nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
+  allow_big_lds(nsf_bwd_rt_attr, nsf_bwd_rt_kernel<4>);
+  return rt_det_workspace(nsf_bwd_rt_kernel<4>, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params);
+}
+
+// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+static int nsf_bwd_rt_run(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                          float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
+                          float tail_bound, int inverse, int n_hidden, const int* hidden, bool det, float* workspace,
+                          int64_t workspace_floats, void* stream) {
   if (!x || !y || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || K < 1 || !(tail_bound > 0.f) ||
       !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
+  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
   if (1e-3 * K > 1.0) return MNF_ERR_DOMAIN;
   if (rows == 0) return MNF_OK;
-  if (deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  if ((!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   NsfBwdRtArgs a;
   memset(&a, 0, sizeof(a));
   RtPlan p;
@@ -323,7 +337,22 @@ extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* gr
   a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
   a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound; a.inverse = inverse != 0;
   a.vec = dim % 8 == 0 && aligned16(x, y, grad_x, grad_y);
-  static DeviceMemo attr;
-  allow_big_lds(attr, nsf_bwd_rt_kernel<4>);
-  return launch_persistent(nsf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "nsf_bwd_rt", (hipStream_t)stream);
+  allow_big_lds(nsf_bwd_rt_attr, nsf_bwd_rt_kernel<4>);
+  return launch_rt_bwd(nsf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params, det, workspace,
+                       workspace_floats, "nsf_bwd_rt", (hipStream_t)stream);
+}
+
+extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                                 float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
+                                 float tail_bound, int inverse, int n_hidden, const int* hidden, void* stream) {
+  return nsf_bwd_rt_run(x, y, grad_y, grad_ld, grad_x, grad_flat, flat, grad_scale_dev, rows, dim, K, tail_bound, inverse,
+                        n_hidden, hidden, false, nullptr, 0, stream);
+}
+
+extern "C" int mnf_nsf_cl_bwd_rt_det(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                                     float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                                     int K, float tail_bound, int inverse, int n_hidden, const int* hidden, float* workspace,
+                                     int64_t workspace_floats, void* stream) {
+  return nsf_bwd_rt_run(x, y, grad_y, grad_ld, grad_x, grad_flat, flat, grad_scale_dev, rows, dim, K, tail_bound, inverse,
+                        n_hidden, hidden, true, workspace, workspace_floats, stream);
 }

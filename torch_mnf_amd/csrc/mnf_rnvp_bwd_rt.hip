@@ -36,6 +36,7 @@ struct RnvpBwdRtArgs {
   int cb, bt, block_words, bias_words;
   int ht_tiles, dt_tiles, ct_tiles;
   NetDesc net;
+  int64_t slot_floats;  // 0; mnf_rnvp_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
 };
 
 __device__ __forceinline__ f32x4 bwd_mask_bits4(uint32_t word, int first_bit) {
@@ -67,7 +68,7 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
   const int hl = nd.sizes[n_hid], MTh = tiles16(hl), KSh = steps32(16 * MTh), M = tiles16(d);
   const int ht_last = exH_tile_of(nd, n_hid);
   const int64_t n_blocks = (a.rows + 16 * nw - 1) / (16 * nw);
-  float* gflat = a.grad_flat;
+  float* const gflat = a.grad_flat + blockIdx.x * a.slot_floats;
 
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
     const int64_t r = blk * (16 * nw) + 16 * wave + j;
@@ -239,13 +240,29 @@ extern "C" int mnf_rnvp_bwd_rt_supported(int dim, int n_hidden, const int* hidde
   return rnvp_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
 }
 
-extern "C" int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
-                               float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows,
-                               int dim, int n_hidden, const int* hidden, void* stream) {
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*rnvp_bwd_rt_kernel_of(const RtPlan& p))(RnvpBwdRtArgs) {
+  static DeviceMemo attr;
+  allow_big_lds(attr, rnvp_bwd_rt_kernel<4>, rnvp_bwd_rt_kernel<8>);
+  return p.mt_max == 4 ? rnvp_bwd_rt_kernel<4> : rnvp_bwd_rt_kernel<8>;
+}
+
+extern "C" int64_t mnf_rnvp_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden) {
+  RnvpBwdRtArgs a;
+  RtPlan p;
+  if (rows < 1 || rows * dim >= (1ll << 40) || !rnvp_bwd_rt_plan(dim, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
+  return rt_det_workspace(rnvp_bwd_rt_kernel_of(p), p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params);
+}
+
+// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+static int rnvp_bwd_rt_run(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
+                           float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                           int n_hidden, const int* hidden, bool det, float* workspace, int64_t workspace_floats, void* stream) {
   if (!z || !grad_z || !flat || !grad_scale_dev || rows < 0 || dim < 1 || n_hidden < 1 || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
+  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (deterministic() || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  if ((!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
   RnvpBwdRtArgs a;
   memset(&a, 0, sizeof(a));
   RtPlan p;
@@ -253,8 +270,21 @@ extern "C" int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed,
   a.z = z; a.mask = mask; a.seed = seed; a.grad_x = grad_x; a.grad_ld = grad_ld; a.grad_z = grad_z; a.grad_flat = grad_flat;
   a.flat = flat; a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim;
   a.vec = dim % 4 == 0 && aligned16(z, grad_z, mask, grad_x);
-  static DeviceMemo attr;
-  allow_big_lds(attr, rnvp_bwd_rt_kernel<4>, rnvp_bwd_rt_kernel<8>);
-  auto kernel = p.mt_max == 4 ? rnvp_bwd_rt_kernel<4> : rnvp_bwd_rt_kernel<8>;
-  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, "rnvp_bwd_rt", (hipStream_t)stream);
+  return launch_rt_bwd(rnvp_bwd_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params, det, workspace,
+                       workspace_floats, "rnvp_bwd_rt", (hipStream_t)stream);
+}
+
+extern "C" int mnf_rnvp_bwd_rt(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
+                               float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows,
+                               int dim, int n_hidden, const int* hidden, void* stream) {
+  return rnvp_bwd_rt_run(z, mask, seed, grad_x, grad_ld, grad_z, grad_flat, flat, grad_scale_dev, rows, dim, n_hidden, hidden,
+                         false, nullptr, 0, stream);
+}
+
+extern "C" int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const float* grad_x, const float* grad_ld,
+                                   float* grad_z, float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows,
+                                   int dim, int n_hidden, const int* hidden, float* workspace, int64_t workspace_floats,
+                                   void* stream) {
+  return rnvp_bwd_rt_run(z, mask, seed, grad_x, grad_ld, grad_z, grad_flat, flat, grad_scale_dev, rows, dim, n_hidden, hidden,
+                         true, workspace, workspace_floats, stream);
 }

@@ -10,8 +10,9 @@
 // after a barrier the (delta tile, H tile) products of the layer are dealt out over the waves -- K = 16 rows per
 // product, three f16 MFMAs for the split form, one wave-tile after the other with its power-of-two scale -- and each
 // finished 16 x 16 block of dW is added to grad_flat with float atomics: ONE flush per row block instead of per tile,
-// no accumulator registers, any layer width.  (Atomic sums: not bit-reproducible run to run; MNF_DETERMINISTIC=1 keeps
-// these shapes on the VALU kernels.)
+// no accumulator registers, any layer width.  (Atomic sums: not bit-reproducible run to run.  The (m, n) pairs go to the
+// waves by shape alone, so one lane makes every add to a given dW / db entry of a workgroup: with a slot of its own per
+// workgroup (mnf_host.h launch_rt_bwd, the *_bwd_rt_det entries) the sums repeat bit for bit.)
 #pragma once
 #include "mnf_rt.h"
 

@@ -273,6 +273,11 @@ bwd_kernel_events: list | None = None  # set to a list to collect (start, end) e
 rnvp_bwd_kernel_events: list | None = None  # likewise for launch B-ts of every RNVP gradient pass
 
 
+def _rt_det_workspace(n: int, grad_flat_ptr, device) -> Tensor | None:
+    """The slots of a run-time-shaped gradient launch's fixed-order form (mnf_*_bwd_rt_det; None: no parameter sums)."""
+    return torch.empty(n, dtype=torch.float32, device=device) if grad_flat_ptr is not None else None
+
+
 def _bwd_split_workspace(lib, f, rows: int, device) -> Tensor | None:
     """Device floats for the split gradient kernel's two-stage flush (one buffer serves every layer of a run)."""
     n = lib.mnf_affine_half_bwd_split_workspace(rows, f.dim, len(f.h_sizes), f._hid)
@@ -345,16 +350,25 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
             and _dispatch.wants_rt(rows, f.force_generic, f._fp32_request()):
         # no per-shape gradient kernel: the run-time-shaped matrix-core one (any 1..4 hidden layers of widths 4..64)
         sc = scale if scale is not None else _grad_scale(gy, gl, rows, f.dim, x_in.device)
-        rc = lib.mnf_affine_half_bwd_rt(
-            x_in.data_ptr(), _ptr(y_out), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, sc.data_ptr(), rows,
-            f.dim, int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift), _stream())
+        args = (x_in.data_ptr(), _ptr(y_out), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, sc.data_ptr(),
+                rows, f.dim, int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift))
+        if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
+            n_ws = lib.mnf_affine_half_bwd_rt_det_workspace(rows, f.dim, *hid, int(f.scale), int(f.shift))
+            if n_ws > 0:
+                ws = _rt_det_workspace(n_ws, grad_flat_ptr, x_in.device)
+                rc = lib.mnf_affine_half_bwd_rt_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
+        else:
+            rc = lib.mnf_affine_half_bwd_rt(*args, _stream())
     if rc == _lib.MNF_ERR_UNSUPPORTED:  # no matrix-core gradient kernel for this shape at all
         rc = lib.mnf_affine_half_bwd(
             x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, rows, f.dim,
             int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift), _stream())
     _lib.check("mnf_affine_half_bwd", rc)
+    shape = f"dim={f.dim}, hidden={f.h_sizes}"
     if not f.force_generic:
-        _lib.note_generic("AffineHalfFlow.backward", rows, f"dim={f.dim}, hidden={f.h_sizes}")
+        _lib.note_generic("AffineHalfFlow.backward", rows, shape)
+    if grad_flat_ptr is not None:
+        _lib.note_atomic_sums("AffineHalfFlow.backward", shape)
     return True
 
 
@@ -470,16 +484,25 @@ class _NsfFn(torch.autograd.Function):
         if _dispatch.NSF_BWD_KERNEL != "generic" and _dispatch.wants_rt(rows, m.force_generic, m._fp32_request()):
             # no per-shape gradient kernel: the run-time-shaped matrix-core one (any dim, K <= 16, hidden widths 4..64)
             scale = _grad_scale(gy, gl, rows, m.dim, x.device)
-            rc = lib.mnf_nsf_cl_bwd_rt(
-                x.data_ptr(), y_out.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
-                scale.data_ptr(), *args, _stream())
+            rt_args = (x.data_ptr(), y_out.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(),
+                       flat.data_ptr(), scale.data_ptr(), *args)
+            rc = _lib.MNF_ERR_UNSUPPORTED
+            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
+                n_ws = lib.mnf_nsf_cl_bwd_rt_det_workspace(rows, m.dim, m.K, len(m.h_sizes), m._hid)
+                if n_ws > 0:
+                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
+                    rc = lib.mnf_nsf_cl_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
+            else:
+                rc = lib.mnf_nsf_cl_bwd_rt(*rt_args, _stream())
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_nsf_cl_bwd_rt", rc)
                 return grad_x, grad_flat, None, None
         _lib.check("mnf_nsf_cl_bwd", lib.mnf_nsf_cl_bwd(
             x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), *args, _stream()))
+        shape = f"dim={m.dim}, K={m.K}, hidden={m.h_sizes}"
         if not m.force_generic and _dispatch.NSF_BWD_KERNEL != "generic" and not m._pad_half():
-            _lib.note_generic("NSF_CL.backward", rows, f"dim={m.dim}, K={m.K}, hidden={m.h_sizes}")
+            _lib.note_generic("NSF_CL.backward", rows, shape)
+        _lib.note_atomic_sums("NSF_CL.backward", shape)
         return grad_x, grad_flat, None, None
 
 
@@ -575,15 +598,23 @@ class _RnvpFn(torch.autograd.Function):
         if not _dispatch.RNVP_BWD_GENERIC and _dispatch.wants_rt(z.shape[0], m.force_generic, m._fp32_request()):
             # no per-shape gradient kernel: the run-time-shaped matrix-core one (1..4 conditioner layers of widths 4..128)
             scale = _grad_scale(gx, gl, z.shape[0], m.dim, z.device)
-            rc = lib.mnf_rnvp_bwd_rt(
-                z.data_ptr(), _ptr(ctx.mask), ctx.seed, _ptr(gx), _ptr(gl), grad_z.data_ptr(), grad_flat.data_ptr(),
-                flat.data_ptr(), scale.data_ptr(), z.shape[0], m.dim, len(m.h_sizes), m._hid, _stream())
+            rt_args = (z.data_ptr(), _ptr(ctx.mask), ctx.seed, _ptr(gx), _ptr(gl), grad_z.data_ptr(), grad_flat.data_ptr(),
+                       flat.data_ptr(), scale.data_ptr(), z.shape[0], m.dim, len(m.h_sizes), m._hid)
+            rc = _lib.MNF_ERR_UNSUPPORTED
+            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
+                n_ws = lib.mnf_rnvp_bwd_rt_det_workspace(z.shape[0], m.dim, len(m.h_sizes), m._hid)
+                if n_ws > 0:
+                    ws = _rt_det_workspace(n_ws, grad_flat, z.device)
+                    rc = lib.mnf_rnvp_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
+            else:
+                rc = lib.mnf_rnvp_bwd_rt(*rt_args, _stream())
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_rnvp_bwd_rt", rc)
                 return grad_z, ret_flat, None, None, None, None
         _lib.check("mnf_rnvp_bwd", lib.mnf_rnvp_bwd(
             z.data_ptr(), _ptr(ctx.mask), ctx.seed, _ptr(gx), _ptr(gl), grad_z.data_ptr(), grad_flat.data_ptr(),
             flat.data_ptr(), z.shape[0], m.dim, len(m.h_sizes), m._hid, _stream()))
+        _lib.note_atomic_sums("RNVP.backward", f"dim={m.dim}, hidden={m.h_sizes}")
         return grad_z, ret_flat, None, None, None, None
 
 
@@ -678,9 +709,9 @@ _NO_PAIR_FUSION_ENV = os.environ.get("MNF_NO_PAIR_FUSION", "0") == "1"
 # fixed-order two-stage reductions instead of float atomics where a kernel has both (the reference's loop repeats bit for
 # bit under torch.manual_seed(0), tests/test_flows.py:11).  The per-shape AffineHalfFlow and NSF_CL gradient kernels
 # reduce in a fixed order in every mode; the switch adds the RNVP, MNFLinear, sample_z and [Glow, ActNorm] launches, and
-# keeps shapes without a per-shape kernel off the run-time-shaped gradient kernels (atomic flushes).  What still adds
-# atomically then: rows that take an fp32 fix-up pass (operands beyond the split range) and the VALU any-shape gradient
-# kernels.
+# runs shapes without a per-shape kernel on the run-time-shaped gradient kernels' fixed-order forms (mnf_*_bwd_rt_det).
+# What still adds atomically then: the VALU any-shape gradient kernels, which warn once per layer and shape
+# (_lib.note_atomic_sums).
 
 
 def _pair_bwd_workspace(rows: int, dim: int, device):
@@ -1317,6 +1348,7 @@ class _NsfArFn(torch.autograd.Function):
         _lib.check("mnf_nsf_ar_bwd", _lib.load().mnf_nsf_ar_bwd(
             x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), x.shape[0],
             m.dim, m.K, float(m.B), int(ctx.inverse), len(m.h_sizes), m._hid, _stream()))
+        _lib.note_atomic_sums("NSF_AR.backward", f"dim={m.dim}, K={m.K}, hidden={m.h_sizes}")
         return grad_x, grad_flat, None, None
 
 
@@ -1591,6 +1623,7 @@ class _MafFn(torch.autograd.Function):
             x.data_ptr(), y.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
             masks.data_ptr(), x.shape[0], m.dim, int(bool(m.parity)), int(ctx.sequential), len(m.h_sizes), m._hid,
             _stream()))
+        _lib.note_atomic_sums(f"{type(m).__name__}.backward", f"dim={m.dim}, hidden={m.h_sizes}")
         return grad_x, ret, None, None, None
 
 
