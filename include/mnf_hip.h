@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 16
+#define MNF_ABI_VERSION 17
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -119,9 +119,9 @@ int mnf_affine_half(const float* x, float* y, float* log_det, int accumulate,
                     int n_hidden, const int* hidden_host, int has_scale, int has_shift,
                     int force_generic, void* stream);
 /* Same layer, additionally writing y_sqnorm[r] = |y_r|^2 (rows,) so that the base log-prob of
- * a standard-normal base needs no second pass over y.  Only the
- * specialised kernel produces it: MNF_ERR_UNSUPPORTED otherwise (callers then run
- * mnf_gauss_logprob on y). */
+ * a standard-normal base needs no second pass over y.  The specialised
+ * kernels and the run-time-shaped kernel (mnf_ahf_rt.hip) produce it; the VALU any-shape kernel does
+ * not: MNF_ERR_UNSUPPORTED where the call would land there (callers then run mnf_gauss_logprob on y). */
 int mnf_affine_half_sq(const float* x, float* y, float* log_det, float* y_sqnorm, int accumulate,
                        const float* flat, const float* image, const void* split_image,
                        int64_t rows, int dim, int parity, int inverse,
@@ -147,6 +147,25 @@ int mnf_affine_half_stack(const float* x, float* y, float* intermediates, float*
                           const float* images, const void* split_images, const int* parity_host, int n_layers,
                           int64_t rows, int dim, int inverse,
                           int n_hidden, const int* hidden_host, void* stream);
+/* n_layers (1 .. 32) AffineHalfFlow layers of one shape WITHOUT a per-shape kernel in ONE launch of the run-time-shaped
+ * kernel (mnf_ahf_rt.hip; kernel family "ahf_stack_rt", "ahf_rt" for one layer).  flats: the layers' plain parameter
+ * vectors back to back, layer 0 first, mnf_affine_half_flat_floats() each -- no operand image, no index table.  Layers
+ * are applied 0..L-1 (forward) or L-1..0 (inverse); one layer's weights are in LDS at a time and every workgroup takes
+ * its own row blocks through all layers, so each layer reads what the same lane wrote.  Everything else as
+ * mnf_affine_half_stack: intermediates NULL (the layers after the first then run in place in y) or (n_layers - 1, rows,
+ * dim) in application order; y_sqnorm / log_prob / log_prob_sum optional (the latter two need log_det; log_prob_sum is
+ * ADDED to, the caller zeroes it).  Results are those of n_layers mnf_affine_half calls with force_generic == 2, bit for
+ * bit (log_det accumulates in the same order).  Runs at any row count; never allocates or synchronises.
+ * MNF_ERR_UNSUPPORTED where mnf_affine_half_rt_stack_supported() is 0 (caller: one launch per layer). */
+int mnf_affine_half_rt_stack(const float* x, float* y, float* intermediates, float* log_det, float* y_sqnorm,
+                             float* log_prob, double* log_prob_sum, int accumulate, const float* flats,
+                             const int* parity_host, int n_layers, int64_t rows, int dim, int inverse,
+                             int n_hidden, const int* hidden_host, int has_scale, int has_shift, void* stream);
+/* Host-side query of the shape alone (no device needed): mnf_affine_half_rt_supported's shapes, n_layers 1 .. 32 --
+ * except, for n_layers > 1, hidden widths beyond 128 whose conditioner does not fit LDS (every row block re-stages the
+ * weights there; one launch for the run measured 4 % slower than one per layer). */
+int mnf_affine_half_rt_stack_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                                       int n_layers);
 /* Split image of one layer: n_split_words 32-bit words of packed f16 (hi | scaled lo) operands, then
  * n_plain_words fp32 words (biases), then MNF_SPLIT_TAIL_WORDS words written by the pack call (word 0
  * = bit pattern of max |weight|: the kernels take the fp32 path when it leaves the f16 range).

@@ -13,6 +13,7 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |--------------------------|-----------------|---------------------------------------------------|--------------------------------|
 | AffineHalfFlow fwd       | any             | 3 hidden layers <= 32 (64 at d = 32/64/128), d <= 256 | ahf_split(_stack) / ahf_mfma |
 |                          | >= RT_MIN_ROWS  | any h_sizes (>= 1 layer, widths 4..256), any d    | ahf_rt                         |
+|                          | >= RT_MIN_ROWS, no grad | a run of 2..32 such layers of one shape   | ahf_stack_rt (one launch)      |
 |                          | else            | anything                                          | ahf_generic (VALU)             |
 | AffineHalfFlow bwd       | >= BWD_SPLIT_MIN_ROWS | the split kernel's shapes                   | ahf_bwd_split                  |
 |                          | any             | the fp32-MFMA kernel's shapes                     | ahf_bwd_mfma_fp32              |
@@ -37,6 +38,11 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
 layer, K <= 8 takes n_h <= 64; K = 9 n_h <= 64 at 1-2 layers, 48 at 3-4; K = 10..12 n_h <= 48 / 32; K = 13..16 n_h <= 32.
+
+The ahf_stack_rt row is flows._AffineRun's second route (mnf_affine_half_rt_stack): a run of equal-shaped AffineHalfFlow
+layers without operand image, inside a NormalizingFlow or FusedAffineStack, under wants_rt() for every layer and with no
+gradients wanted -- every intermediate and log_det bit for bit those of one ahf_rt launch per layer, plus the log-prob
+epilogue when the run closes a density pass.  With gradients wanted the layers run one by one as the rows above say.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and

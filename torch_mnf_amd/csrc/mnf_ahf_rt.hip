@@ -7,6 +7,15 @@
 // A wave owns NTL 16-row tiles: the s-net and the t-net run one after the other up to their last hidden vectors (the
 // conditioning half streamed from memory K-step by K-step, copied to y on the way), then the output layer is walked
 // tile by tile: s and t of 16 columns, the affine transform of those columns, the row's log|det J| in registers.
+//
+// A RUN of n_layers layers of one shape (mnf_affine_half_rt_stack) is the same kernel with a layer loop: one layer's
+// weights are resident (or streamed) at a time, and the workgroup sweeps ITS OWN row blocks once per layer.  Lane (j, q)
+// of a wave stores exactly the elements of row j that it loads -- conditioning half columns 32 ks + 4 q + r and
+// 32 ks + 16 + 4 q + r, transformed half columns 16 m + 4 q + r: in both the lane is (col mod 16) / 4 -- and the row block
+// -> wave -> tile mapping is the same in every layer, so everything layer l + 1 loads was stored by the same lane in
+// layer l: the hand-over through memory needs no barrier, no fence and no grid-wide synchronisation (lanes of rows past
+// the end and out-of-range column pieces read clamped addresses that other lanes write; selects drop those values).
+// Without an intermediates buffer the layers after the first run in place in y by the same ownership.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -19,11 +28,16 @@ namespace mnf {
 struct AhfRtArgs {
   const float* x;
   float* y;
+  float* mid;                // (n_layers - 1, rows, dim): every layer's output but the last, or NULL (in place in y)
   float* log_det;
   float* ysq;
-  const float* flat;
+  float* log_prob;           // the standard-normal epilogue on the last applied layer: log_prob[r] and / or ...
+  double* lp_sum;            // ... its sum over rows, ADDED (one atomic per wave)
+  const float* flat;         // n_layers parameter vectors of n_params floats back to back, model order
   int64_t rows;
-  int dim, parity, inverse, accumulate, has_scale, has_shift;
+  uint32_t parity;           // bit l: layer l's parity
+  int n_layers;
+  int dim, inverse, accumulate, has_scale, has_shift;
   int n_params;
   int vec;                   // rows and halves are 16-byte aligned: dwordx4 row accesses
   int cb, bt;                // LDS plan (mnf_rt.h Source)
@@ -31,14 +45,29 @@ struct AhfRtArgs {
   NetDesc s_net, t_net;
 };
 
+// what changes from layer to layer of a run (the by-value AhfRtArgs stays constant: it lives in scalar registers)
+struct AhfRtLayer {
+  const float* x;
+  float* y;
+  const float* flat;
+  float* ysq;
+  float* log_prob;
+  int parity, accumulate, lp;  // lp: this layer ends with the log-prob epilogue (log_prob and / or the sum)
+};
+
 constexpr float kLog2e = 1.4426950408889634f;
 
+// A wave's running fp64 log-prob sum: the 16 floats in front of the blocks, which block_weight_max is done with once it
+// has returned (8 waves x 8 bytes)
+extern __shared__ __attribute__((aligned(16))) uint32_t rt_lds[];
+__device__ __forceinline__ double* lp_slot(int wave) { return reinterpret_cast<double*>(rt_lds) + wave; }
+
 template <int MT_MAX, int NTL, int VEC, bool PREFILL, typename Src>  // VEC: 0 / 1, or 2 = a.vec
-__device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float wup, int64_t row0) {
+__device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, const AhfRtLayer& ly, Src& src, float wup, int64_t row0) {
   using namespace rt;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
   const int H = a.dim / 2;
-  const int cond_off = a.parity ? H : 0, act_off = a.parity ? 0 : H;
+  const int cond_off = ly.parity ? H : 0, act_off = ly.parity ? 0 : H;
   const bool vec = VEC == 2 ? a.vec != 0 : VEC == 1;
   const float* xrow[NTL];
   float* yrow[NTL];
@@ -48,8 +77,8 @@ __device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float
     const int64_t r = row0 + (int64_t)(wave * NTL + t) * 16 + j;
     live[t] = !PREFILL && r < a.rows;
     const int64_t rc = r < a.rows ? r : a.rows - 1;
-    xrow[t] = a.x + rc * a.dim;
-    yrow[t] = a.y + rc * a.dim;
+    xrow[t] = ly.x + rc * a.dim;
+    yrow[t] = ly.y + rc * a.dim;
   }
   float sq[NTL];
 #pragma unroll
@@ -77,11 +106,11 @@ __device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float
     };
     const NetDesc* const nds[2] = {&a.s_net, &a.t_net};
     Hidden<MT_MAX, NTL> h2[2];
-    first_layer<MT_MAX, NTL, PREFILL, 2>(src, a.flat, nds, n_hid != 0, wup, lane, q, load_x, use_x, h2);
+    first_layer<MT_MAX, NTL, PREFILL, 2>(src, ly.flat, nds, n_hid != 0, wup, lane, q, load_x, use_x, h2);
     hs = h2[0];
     ht = h2[1];
-    hidden_layers<MT_MAX, NTL, PREFILL>(src, a.flat, a.s_net, n_hid, -1, wup, lane, q, hs);
-    hidden_layers<MT_MAX, NTL, PREFILL>(src, a.flat, a.t_net, n_hid, -1, wup, lane, q, ht);
+    hidden_layers<MT_MAX, NTL, PREFILL>(src, ly.flat, a.s_net, n_hid, -1, wup, lane, q, hs);
+    hidden_layers<MT_MAX, NTL, PREFILL>(src, ly.flat, a.t_net, n_hid, -1, wup, lane, q, ht);
   } else {
 #pragma unroll 1
     for (int net = 0; net < n_nets; ++net) {
@@ -96,7 +125,7 @@ __device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float
       };
       // (s_net, t_net are both filled: an absent net is a copy of the other one; net 0 = the first PRESENT net)
       if (net == 1) hs = ht;  // (both nets present: the s-net's vector moves over, the t-net's takes its place)
-      net_to_hidden<MT_MAX, NTL, PREFILL>(src, a.flat, net == 0 && a.has_scale ? a.s_net : a.t_net, n_hid, -1, wup, lane, q,
+      net_to_hidden<MT_MAX, NTL, PREFILL>(src, ly.flat, net == 0 && a.has_scale ? a.s_net : a.t_net, n_hid, -1, wup, lane, q,
                                           load_x, use_x, ht);
     }
   }
@@ -109,8 +138,8 @@ __device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float
   int MO = Src::resident ? M : src.cb / (heads * KS);
   if (MO > src.bt / heads && !Src::resident) MO = src.bt / heads;
   if (MO < 1) MO = 1;
-  const float* W0 = a.flat + any_net.w_off[L];
-  const float* B0 = a.flat + any_net.b_off[L];
+  const float* W0 = ly.flat + any_net.w_off[L];
+  const float* B0 = ly.flat + any_net.b_off[L];
   const int64_t w_stride = (int64_t)a.t_net.w_off[L] - a.s_net.w_off[L], b_stride = (int64_t)a.t_net.b_off[L] - a.s_net.b_off[L];
   float ld[NTL];
 #pragma unroll
@@ -183,33 +212,63 @@ __device__ __forceinline__ void ahf_rt_block(const AhfRtArgs& a, Src& src, float
     const float total = sum_over_q(a.inverse ? -ld[t] : ld[t]);  // log_det = s.sum(1), sign flipped on the way back (:55, :62)
     const float sqt = sum_over_q(sq[t]);
     if (q == 0 && live[t]) {
-      if (a.log_det) a.log_det[r] = a.accumulate ? a.log_det[r] + total : total;
-      if (a.ysq) a.ysq[r] = sqt;
+      float ld_row = total;
+      if (a.log_det) {
+        if (ly.accumulate) ld_row = a.log_det[r] + total;
+        a.log_det[r] = ld_row;
+      }
+      if (ly.ysq) ly.ysq[r] = sqt;
+      if (ly.lp) {  // log N(y_r; 0, I) + log_det, as gauss_logprob_sq_kernel (mnf_generic.hip) forms it
+        const float lp = ld_row + (-0.5f * sqt - (float)a.dim * kHalfLog2Pi);
+        if (ly.log_prob) ly.log_prob[r] = lp;
+        if (a.lp_sum) atomicAdd(lp_slot(wave), (double)lp);  // the wave's fp64 slot in LDS
+      }
     }
   }
 }
 
 template <int MT_MAX, int NTL, int NW, bool RESIDENT, int VEC>
 __global__ void __launch_bounds__(NW * 64) ahf_rt_kernel(AhfRtArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t rt_lds[];
   float* scratch = reinterpret_cast<float*>(rt_lds);
   uint32_t* blocks = rt_lds + 16;
   float* bias = reinterpret_cast<float*>(blocks + a.block_words);
-  const float wmax = rt::block_weight_max(a.flat, a.n_params, scratch);
-  const int e = rt::weight_exponent(wmax);  // weights are staged as w 2^-e: the largest one just below 2^15
-  const float wup = rt::pow2f(e);
-  rt::Source<RESIDENT> src{blocks, bias, a.cb, a.bt, 0, 0, 0, rt::pow2f(-e), 0};
-  if (RESIDENT) {
-    ahf_rt_block<MT_MAX, NTL, VEC, true>(a, src, wup, 0);
-    __syncthreads();
-  }
+  rt::Source<RESIDENT> src{blocks, bias, a.cb, a.bt, 0, 0, 0, 1.f, 0};
   const int64_t rows_per_block = (int64_t)(blockDim.x >> 6) * NTL * 16;
   const int64_t n_blocks = (a.rows + rows_per_block - 1) / rows_per_block;
-  for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
-    src.slot = 0;
-    src.btile = 0;
-    ahf_rt_block<MT_MAX, NTL, VEC, false>(a, src, wup, b * rows_per_block);
+  const int64_t plane = a.rows * a.dim;
+  // layers outermost: one layer's weights in LDS at a time; the workgroup keeps its row blocks through all layers
+#pragma unroll 1
+  for (int i = 0; i < a.n_layers; ++i) {
+    const int l = a.inverse ? a.n_layers - 1 - i : i;
+    const bool last = i == a.n_layers - 1;
+    AhfRtLayer ly;
+    ly.x = i == 0 ? a.x : a.mid ? a.mid + (i - 1) * plane : a.y;
+    ly.y = last || !a.mid ? a.y : a.mid + i * plane;
+    ly.flat = a.flat + (int64_t)l * a.n_params;
+    ly.ysq = last ? a.ysq : nullptr;
+    ly.log_prob = last ? a.log_prob : nullptr;
+    ly.lp = last && (a.log_prob || a.lp_sum);
+    ly.parity = (a.parity >> l) & 1u;
+    ly.accumulate = i > 0 || a.accumulate;
+    // (the two barriers in here also keep this layer's staging behind the other waves' last reads of the previous one's)
+    const float wmax = rt::block_weight_max(ly.flat, a.n_params, scratch);
+    const int e = rt::weight_exponent(wmax);  // weights are staged as w 2^-e: the largest one just below 2^15
+    const float wup = rt::pow2f(e);
+    src.wdown = rt::pow2f(-e);
+    if (ly.lp && a.lp_sum && (threadIdx.x & 63) == 0) lp_slot(threadIdx.x >> 6)[0] = 0.0;
+    if (RESIDENT) {
+      src.slot = 0;
+      src.btile = 0;
+      ahf_rt_block<MT_MAX, NTL, VEC, true>(a, ly, src, wup, 0);
+      __syncthreads();
+    }
+    for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+      src.slot = 0;
+      src.btile = 0;
+      ahf_rt_block<MT_MAX, NTL, VEC, false>(a, ly, src, wup, b * rows_per_block);
+    }
   }
+  if (a.lp_sum && (threadIdx.x & 63) == 0) atomicAdd(a.lp_sum, lp_slot(threadIdx.x >> 6)[0]);
 }
 
 // The launch of a shape (`aligned`: x and y 16-byte aligned), or false: the VALU kernel takes it.  Fills the kernel
@@ -267,24 +326,46 @@ static int ahf_rt_launch_class(const AhfRtArgs& a, const RtPlan& p, hipStream_t 
                 ahf_rt_kernel<MT_MAX, 1, NW, true, 0>);
   auto kernel = !p.resident ? ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>
                             : a.vec ? ahf_rt_kernel<MT_MAX, 1, NW, true, 1> : ahf_rt_kernel<MT_MAX, 1, NW, true, 0>;
-  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, "ahf_rt", stream);
+  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, a.n_layers > 1 ? "ahf_stack_rt" : "ahf_rt", stream);
 }
 
-// MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
-int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const float* flat, int64_t rows,
-                  int dim, int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
-                  hipStream_t stream) {
-  if (!flat || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+// Which runs go out as one launch: 1 .. 32 layers of a shape the kernel has.  Measured out: runs of the widest class's
+// STREAMING shapes (hidden widths 129 .. 256 whose conditioner does not fit LDS: every row block re-stages the weights, the
+// pass is bound by that staging, and nine layers in one launch were 4 % slower than nine launches -- 9.17 against 8.80 ns
+// per row and layer at dim = 256, (200, 130, 40, 7), 262,144 rows); one layer of them is today's call.
+static bool ahf_rt_stack_ok(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, int n_layers) {
+  AhfRtArgs a;
+  RtPlan p;
+  if (n_layers < 1 || n_layers > 32 || !ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p)) return false;
+  return n_layers == 1 || p.resident || p.mt_max != 16;
+}
+
+// A run of n_layers layers (see the head of this file; n_layers = 1: mid, log_prob, lp_sum NULL and `flats` the layer's
+// vector).  MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too.
+int ahf_rt_stack_launch(const float* x, float* y, float* mid, float* log_det, float* ysq, float* log_prob, double* lp_sum,
+                        int accumulate, const float* flats, uint32_t parity_bits, int n_layers, int64_t rows, int dim,
+                        int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift, hipStream_t stream) {
+  if (!flats || rows * dim >= (1ll << 40) || (n_layers > 1 && rows * dim * (n_layers - 1) >= (1ll << 42)))
+    return MNF_ERR_UNSUPPORTED;
   AhfRtArgs a;
   memset(&a, 0, sizeof(a));
   RtPlan p;
-  if (!ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, aligned16(x, y), a, p)) return MNF_ERR_UNSUPPORTED;
-  a.x = x; a.y = y; a.log_det = log_det; a.ysq = ysq; a.flat = flat; a.rows = rows; a.dim = dim;
-  a.parity = parity != 0; a.inverse = inverse != 0; a.accumulate = accumulate != 0;
+  if (!ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, aligned16(x, y, mid), a, p)) return MNF_ERR_UNSUPPORTED;
+  a.x = x; a.y = y; a.mid = n_layers > 1 ? mid : nullptr; a.log_det = log_det; a.ysq = ysq; a.log_prob = log_prob;
+  a.lp_sum = lp_sum; a.flat = flats; a.rows = rows; a.dim = dim; a.parity = parity_bits; a.n_layers = n_layers;
+  a.inverse = inverse != 0; a.accumulate = accumulate != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
   if (p.mt_max == 4) return ahf_rt_launch_class<4, 8>(a, p, stream);
   if (p.mt_max == 8) return ahf_rt_launch_class<8, 8>(a, p, stream);
   return ahf_rt_launch_class<16, 4>(a, p, stream);
+}
+
+// one layer; MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
+int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const float* flat, int64_t rows,
+                  int dim, int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
+                  hipStream_t stream) {
+  return ahf_rt_stack_launch(x, y, nullptr, log_det, ysq, nullptr, nullptr, accumulate, flat, parity ? 1u : 0u, 1, rows, dim,
+                             inverse, n_hidden, hidden, has_scale, has_shift, stream);
 }
 
 }  // namespace mnf
@@ -293,4 +374,29 @@ extern "C" int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hi
   mnf::AhfRtArgs a;
   mnf::RtPlan p;
   return mnf::ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+}
+
+extern "C" int mnf_affine_half_rt_stack_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
+                                                  int n_layers) {
+  return mnf::ahf_rt_stack_ok(dim, n_hidden, hidden, has_scale, has_shift, n_layers) ? 1 : 0;
+}
+
+extern "C" int mnf_affine_half_rt_stack(const float* x, float* y, float* intermediates, float* log_det, float* y_sqnorm,
+                                        float* log_prob, double* log_prob_sum, int accumulate, const float* flats,
+                                        const int* parity_host, int n_layers, int64_t rows, int dim, int inverse,
+                                        int n_hidden, const int* hidden, int has_scale, int has_shift, void* stream) {
+  if (!x || !y || x == y || !flats || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || dim < 2 || (dim & 1) ||
+      !mnf::hidden_ok(n_hidden, hidden) || (!has_scale && !has_shift) || ((log_prob || log_prob_sum) && !log_det) ||
+      (intermediates && (intermediates == x || intermediates == y)) ||
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(intermediates) |
+        reinterpret_cast<uintptr_t>(flats) | reinterpret_cast<uintptr_t>(log_det) | reinterpret_cast<uintptr_t>(y_sqnorm) |
+        reinterpret_cast<uintptr_t>(log_prob)) & 3) ||
+      (reinterpret_cast<uintptr_t>(log_prob_sum) & 7))
+    return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  if (!mnf_affine_half_rt_stack_supported(dim, n_hidden, hidden, has_scale, has_shift, n_layers)) return MNF_ERR_UNSUPPORTED;
+  uint32_t bits = 0;
+  for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
+  return mnf::ahf_rt_stack_launch(x, y, intermediates, log_det, y_sqnorm, log_prob, log_prob_sum, accumulate, flats, bits,
+                                  n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, (hipStream_t)stream);
 }

@@ -1148,13 +1148,22 @@ class AffineHalfFlow(_TwoWayFlow):
             _lib.note_generic("AffineHalfFlow", x.shape[0], f"dim={self.dim}, hidden={self.h_sizes}")
         return y, (None if accum is not None else ld)
 
-    def emits_sqnorm(self, device) -> bool:
-        """True when this layer's kernel can also write |y_row|^2 (the specialised kernels only; a half narrower than
-        its MFMA tile only has the split stack kernel, so not when that one is switched off)."""
-        if self.force_generic:
+    def emits_sqnorm(self, device, rows: int | None = None) -> bool:
+        """True when this layer's kernel can also write |y_row|^2: the specialised kernels (a half narrower than its
+        MFMA tile only has the split stack kernel, so not when that one is switched off) and, for a shape without
+        them, the run-time-shaped kernel -- the VALU kernel cannot, so that answer needs the call's row count."""
+        if self.force_generic == 1:
             return False
         _, image, split = self._packed3(device)
-        return image is not None and (split is not None or self.dim // 2 in (16, 32, 64, 128))
+        if image is None or self.force_generic == 2:
+            if rows is None or self._force_code(image) == 1 or not _dispatch.wants_rt(rows, self.force_generic, self._fp32_request()):
+                return False
+            ok = self.__dict__.get("_rt_shape_ok")
+            if ok is None:
+                ok = self.__dict__["_rt_shape_ok"] = bool(_lib.load().mnf_affine_half_rt_supported(
+                    self.dim, len(self.h_sizes), self._hid, int(self.scale), int(self.shift)))
+            return ok
+        return split is not None or self.dim // 2 in (16, 32, 64, 128)
 
     def forward(self, z: Tensor, inverse: bool = False) -> tuple[Tensor, Tensor]:
         return self._run(z, inverse, None)
@@ -2111,7 +2120,9 @@ class FusedSplineBlock(_TwoWayFlow):
 
 class _AffineRun:
     """Consecutive ``AffineHalfFlow`` layers of one shape, in MODEL order, as one ``mnf_affine_half_stack``
-    launch.  A plain object (not a Module): it only caches the concatenated operand images."""
+    launch -- or, for a shape without operand image (no per-shape kernel), one ``mnf_affine_half_rt_stack`` launch of
+    the run-time-shaped kernel when no gradients are wanted.  A plain object (not a Module): it only caches the
+    concatenated operand images / parameters."""
 
     MAX_LAYERS = 32  # mnf_affine_half_stack takes the layers' parities as one 32-bit word
 
@@ -2131,6 +2142,9 @@ class _AffineRun:
         self._grad_i0 = None     # index of the run's first parameter in FlatParameters.params
         self._home_now = None    # the flat home of the call in flight (set by launch_grad, read by _AffineRunFn)
         self._stand_in = None
+        self._rt_key = None      # the run-time-shaped route: key and tensor of the concatenated parameters
+        self._rt_flat: Tensor | None = None
+        self._rt_shape_ok = None  # mnf_affine_half_rt_stack_supported, asked once
 
     @staticmethod
     def compatible(a: "AffineHalfFlow", b: "AffineHalfFlow") -> bool:
@@ -2240,15 +2254,54 @@ class _AffineRun:
             flat.data_ptr(), idx.data_ptr(), images.data_ptr(), n_split, n_plain, n, flat.numel() // n, _stream()))
         return images, words
 
+    def rt_route(self, rows: int, device) -> bool:
+        """True when a no-grad pass of ``rows`` rows goes out as ONE launch of the run-time-shaped kernel
+        (``mnf_affine_half_rt_stack``): the shape has no operand image (or every layer is forced onto the run-time-shaped
+        tier, ``force_generic == 2``, whatever its per-shape kernels), no layer asks for the VALU kernel
+        (``force_generic == 1``) or for fp32 arithmetic (that tier is split-f16), the library has the shape, and the
+        single layer would land on ``ahf_rt`` too (``_dispatch.wants_rt``: from RT_MIN_ROWS rows on, or every layer
+        ``force_generic == 2``)."""
+        f0 = self.layers[0]
+        if any(f.force_generic == 1 or f._fp32_request() for f in self.layers):
+            return False
+        if not _dispatch.wants_rt(rows, 2 if all(f.force_generic == 2 for f in self.layers) else 0):
+            return False
+        if f0._device_index(device) is not None and not all(f.force_generic == 2 for f in self.layers):
+            return False  # (a shape with per-shape kernels is here only when every layer is forced onto this tier)
+        if self._rt_shape_ok is None:
+            self._rt_shape_ok = bool(_lib.load().mnf_affine_half_rt_stack_supported(
+                f0.dim, len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), len(self.layers)))
+        return self._rt_shape_ok
+
+    def rt_flat(self, device) -> Tensor:
+        """The layers' plain parameter vectors back to back (model order) for the run-time-shaped route: the live slice
+        of the FlatParameters buffer when the run lives in one, else one concatenation per weight update (keyed like
+        ``images()``: every parameter's (data_ptr, _version))."""
+        params = self._params()
+        home = self.flat_home()
+        if home is not None and home[0].data.device == device and home[0].data.dtype == torch.float32:
+            return home[0].data[home[1]:home[1] + home[2]]
+        key = (device, [(p.data_ptr(), p._version) for p in params])
+        if key != self._rt_key:
+            flat = torch.cat([p.detach().reshape(-1) for p in params])
+            self._rt_flat = flat.to(device=device, dtype=torch.float32).contiguous()
+            self._rt_key = key
+        return self._rt_flat
+
     def ready(self, x):
-        """The run's (fp32 images, split images) if ``x`` can go through the stack kernel without gradients, else
-        None.  Hand the result to ``launch(images=...)``: the cache is then validated once per pass, not twice."""
-        if (self._unsupported or not isinstance(x, Tensor) or not x.is_cuda or x.dim() != 2 or x.shape[0] == 0
-                or x.shape[1] != self.layers[0].dim or any(f.force_generic for f in self.layers)
-                or any(_wants_grad(f, x) for f in self.layers)):
+        """The run's (fp32 images, split images) if ``x`` can go through the stack kernel without gradients --
+        ("rt", parameters) if it goes through the run-time-shaped kernel instead -- else None.  Hand the result to
+        ``launch(images=...)``: the cache is then validated once per pass, not twice."""
+        if (not isinstance(x, Tensor) or not x.is_cuda or x.dim() != 2 or x.shape[0] == 0
+                or x.shape[1] != self.layers[0].dim or any(_wants_grad(f, x) for f in self.layers)):
             return None
-        imgs = self.images(x.device)
-        return imgs if imgs[0] is not None else None
+        if not self._unsupported and not any(f.force_generic for f in self.layers):
+            imgs = self.images(x.device)
+            if imgs[0] is not None:
+                return imgs
+        if self.rt_route(x.shape[0], x.device):
+            return ("rt", self.rt_flat(x.device))
+        return None
 
     def usable(self, x) -> bool:
         return self.ready(x) is not None
@@ -2305,7 +2358,13 @@ class _AffineRun:
         standard-normal log-prob epilogue too; ``self.logprob_fused`` says whether it did (only the split
         kernel can -- otherwise ``sqnorm`` is filled as usual and the caller runs the epilogue kernel)."""
         f0, n = self.layers[0], len(self.layers)
-        images, splits = images if images is not None else self.images(x.device)  # (``images``: from ready())
+        if images is None:
+            images = self.ready(x)
+            if images is None:
+                return None
+        if isinstance(images[0], str):  # the run-time-shaped route
+            return self._launch_rt(x, inverse, log_det, accumulate, sqnorm, keep, logprob, images[1])
+        images, splits = images  # (``images``: from ready())
         x = _device_input(x, "input")
         buf = torch.empty((n if keep else 1, x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
         par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
@@ -2326,6 +2385,25 @@ class _AffineRun:
             self._unsupported = True
             return None
         _lib.check("mnf_affine_half_stack", rc)
+        return list(buf.unbind(0))
+
+    def _launch_rt(self, x, inverse, log_det, accumulate, sqnorm, keep, logprob, flat) -> list[Tensor] | None:
+        """``launch`` on the run-time-shaped kernel: same buffers, the parameters instead of operand images.  Every
+        shape it takes has the log-prob epilogue."""
+        f0, n = self.layers[0], len(self.layers)
+        x = _device_input(x, "input")
+        buf = torch.empty((n if keep else 1, x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+        par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
+        self.logprob_fused = logprob is not None and not _dispatch.NO_FUSED_LOGPROB
+        lp, total, sq = (logprob[0], logprob[1], None) if self.logprob_fused else (None, None, sqnorm)
+        rc = _lib.load().mnf_affine_half_rt_stack(
+            x.data_ptr(), buf[-1].data_ptr(), buf.data_ptr() if keep and n > 1 else None, log_det.data_ptr(), _ptr(sq),
+            _ptr(lp), _ptr(total), int(accumulate), flat.data_ptr(), par, n, x.shape[0], f0.dim, int(inverse),
+            len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), _stream())
+        if rc == _lib.MNF_ERR_UNSUPPORTED:
+            self._rt_shape_ok, self.logprob_fused = False, False
+            return None
+        _lib.check("mnf_affine_half_rt_stack", rc)
         return list(buf.unbind(0))
 
 
@@ -2361,7 +2439,7 @@ class FusedAffineStack(_TwoWayFlow):
     def invalidate(self) -> None:
         super().invalidate()
         for r in self._run_helpers:
-            r._key = None
+            r._key = r._rt_key = None
 
     def _sequence(self, x, inverse, sqnorm=None):
         ld = 0
@@ -2371,7 +2449,11 @@ class FusedAffineStack(_TwoWayFlow):
             ld = ld + l1
         return x, ld
 
-    def emits_sqnorm(self, device) -> bool:
+    def emits_sqnorm(self, device, rows: int | None = None) -> bool:
+        """``rows``: the call's row count -- a stack without per-shape kernels emits |y|^2 where the call lands on the
+        run-time-shaped kernel, which depends on it."""
+        if self.layers[0]._device_index(device) is None:
+            return rows is not None and all(r.rt_route(rows, device) for r in self._run_helpers)
         return all(r.images(device)[0] is not None for r in self._run_helpers)
 
     def _run(self, x, inverse, accum, sqnorm: Tensor | None = None, overwrite: bool = False):
@@ -2556,6 +2638,11 @@ class NormalizingFlow(nn.Module):
             if run is not None and not train_run:
                 if isinstance(run, _AffineRun):
                     run_images = run.ready(x)
+                    if run_images is not None and isinstance(run_images[0], str) and events_on:
+                        # per-launch event marks are being collected (bench.py): the run-time-shaped run stays one
+                        # `ahf_rt` launch per layer, which is what the marks of such a model have always described
+                        # (bench.py labels a mark that spans several layers as the per-shape stack kernel)
+                        run_images = None
                     if run_images is None:
                         run = None
                 elif not run.usable(x, inverse):
@@ -2607,7 +2694,7 @@ class NormalizingFlow(nn.Module):
                 span, outs = 2, [x]
             if outs is None:
                 if (want_sqnorm and last and isinstance(flow, (AffineHalfFlow, FusedAffineStack))
-                        and x.is_cuda and x.shape[0] > 0 and not _wants_grad(flow, x) and flow.emits_sqnorm(x.device)):
+                        and x.is_cuda and x.shape[0] > 0 and not _wants_grad(flow, x) and flow.emits_sqnorm(x.device, x.shape[0])):
                     # last layer also emits |z|^2 per row for the standard-normal epilogue
                     self._last_sqnorm = torch.empty(x.size(0), device=x.device)
                     x, _ = flow._run(x, inverse, log_det, self._last_sqnorm, overwrite=fresh and i == 0)
