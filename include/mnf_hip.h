@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 17
+#define MNF_ABI_VERSION 18
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -627,6 +627,49 @@ int mnf_affine_half_bwd_rt_det(const float* x, const float* y, const float* grad
                                float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
                                int parity, int inverse, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
                                float* workspace, int64_t workspace_floats, void* stream);
+/* The gradients of a RUN of n_layers (1 .. 32) AffineHalfFlow layers of one shape in ONE launch of the same kernel (a
+ * layer loop outermost, applied layers n_layers - 1 .. 0; kernel family ahf_bwd_stack_rt, one layer: ahf_bwd_rt): the
+ * backward pass of mnf_affine_half_rt_stack.  Every workgroup keeps its row blocks through all layers, and the grad_x a
+ * lane stores for applied layer i is the grad_y the same lane loads for layer i - 1: no grid-wide synchronisation.
+ *   x               the input of the first applied layer
+ *   outs            (n_layers, rows, dim): every applied layer's output in application order -- what
+ *                   mnf_affine_half_rt_stack leaves in `intermediates` followed by `y` when they are one buffer.  Applied
+ *                   layer i reads its input from x (i = 0) or outs[i - 1] and its output (inverse direction: g_s) from outs[i]
+ *   flats           the layers' plain parameter vectors back to back in MODEL order (applied order reversed when inverse)
+ *   grad_flats      the same layout, ADDED to (float atomics; NULL: grad_x only)
+ *   parity_host     host ints, MODEL order
+ *   cotangents, exactly one of two forms (MNF_ERR_INVALID_ARG when both are given):
+ *     (a) grad_y_last (rows x dim; may be NULL) on the last applied layer's output and grad_ld (rows; may be NULL) on the
+ *         run's log_det -- the layers' sum, so every layer receives the same grad_ld;
+ *     (b) lp_grad (rows) = d loss / d log p with log p = log_det + log N(outs[n_layers - 1]; 0, I): every layer's grad_ld
+ *         is lp_grad and the last applied layer's grad_y = -outs[n_layers - 1] lp_grad is formed where the kernel loads
+ *         grad_y (no `-z g` pass, no grad_y tensor; bit for bit form (a) on that tensor).
+ *   grad_x          (rows x dim) the gradient with respect to x; also one of the two planes the cotangent alternates
+ *                   between from layer to layer (never in place: the forward direction's t pass reads grad_y of the
+ *                   transformed half after grad_x has been stored there)
+ *   grad_work       the other plane: rows x dim floats of caller scratch, uninitialised (NULL allowed for n_layers = 1)
+ *   grad_scale_dev  n_layers device floats, entry i the power of two for APPLIED layer i (each as
+ *                   mnf_affine_half_grad_scale gives it for that layer's cotangents).  The kernel's results depend on the
+ *                   scale in their last bit, so a caller that wants the bits of n single-layer calls passes the scales
+ *                   those calls would get; one value repeated n_layers times is as valid
+ * MNF_ERR_UNSUPPORTED where mnf_affine_half_bwd_rt_stack_supported() is 0 (mnf_affine_half_bwd_rt_supported()'s shapes
+ * with n_layers 1 .. 32; host only) or MNF_DETERMINISTIC is set (atomic sums).  The _det form, callable in either mode,
+ * gives every workgroup a slot of n_layers x n_params floats and adds the slots up in order, as mnf_affine_half_bwd_rt_det:
+ * bit for bit what n_layers calls of that entry give. */
+int mnf_affine_half_bwd_rt_stack_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                                           int n_layers);
+int mnf_affine_half_bwd_rt_stack(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
+                                 const float* grad_ld, float* grad_x, float* grad_work, float* grad_flats,
+                                 const float* flats, const float* grad_scale_dev, const int* parity_host, int n_layers,
+                                 int64_t rows, int dim, int inverse, int n_hidden, const int* hidden_host, int has_scale,
+                                 int has_shift, void* stream);
+int64_t mnf_affine_half_bwd_rt_stack_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host,
+                                                   int has_scale, int has_shift, int n_layers);
+int mnf_affine_half_bwd_rt_stack_det(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
+                                     const float* grad_ld, float* grad_x, float* grad_work, float* grad_flats,
+                                     const float* flats, const float* grad_scale_dev, const int* parity_host, int n_layers,
+                                     int64_t rows, int dim, int inverse, int n_hidden, const int* hidden_host, int has_scale,
+                                     int has_shift, float* workspace, int64_t workspace_floats, void* stream);
 int mnf_nsf_cl_bwd(const float* x, const float* grad_y, const float* grad_ld, float* grad_x,
                    float* grad_flat, const float* flat, int64_t rows, int dim, int K, float tail_bound,
                    int inverse, int n_hidden, const int* hidden_host, void* stream);

@@ -18,6 +18,7 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | AffineHalfFlow bwd       | >= BWD_SPLIT_MIN_ROWS | the split kernel's shapes                   | ahf_bwd_split                  |
 |                          | any             | the fp32-MFMA kernel's shapes                     | ahf_bwd_mfma_fp32              |
 |                          | >= RT_MIN_ROWS  | 1..4 hidden layers of widths 4..64, any d         | ahf_bwd_rt                     |
+|                          | >= RT_MIN_ROWS, fuse_rt_training | a run of 2..32 such layers of one shape | ahf_bwd_stack_rt (one launch) |
 |                          | else            | anything                                          | ahf_bwd_generic                |
 | NSF_CL fwd               | any             | d % 8 == 0 up to 64, n_h <= 16, K 5/8 (10: d<=32) | nsf_mfma_split                 |
 |                          | >= NSF_PAD_MIN_ROWS | other d <= 64 (zero-padded twin layer)        | nsf_mfma_split                 |
@@ -42,7 +43,11 @@ layer, K <= 8 takes n_h <= 64; K = 9 n_h <= 64 at 1-2 layers, 48 at 3-4; K = 10.
 The ahf_stack_rt row is flows._AffineRun's second route (mnf_affine_half_rt_stack): a run of equal-shaped AffineHalfFlow
 layers without operand image, inside a NormalizingFlow or FusedAffineStack, under wants_rt() for every layer and with no
 gradients wanted -- every intermediate and log_det bit for bit those of one ahf_rt launch per layer, plus the log-prob
-epilogue when the run closes a density pass.  With gradients wanted the layers run one by one as the rows above say.
+epilogue when the run closes a density pass.  With gradients wanted the layers run one by one as the rows above say --
+unless the owner's opt-in switch ``fuse_rt_training`` (NormalizingFlow / FusedAffineStack, default False) is on: the run
+is then ONE autograd node (flows._AffineRunFn), ahf_stack_rt forward with every output kept and ONE ahf_bwd_stack_rt
+launch backward (mnf_affine_half_bwd_rt_stack; its fixed-order form under MNF_DETERMINISTIC=1), the last layer's
+cotangents formed in the kernel when the run is a whole log_prob pass.  tier() is unchanged by the switch.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and

@@ -787,6 +787,41 @@ class _LinearRowsFn(torch.autograd.Function):
         return gx, gW
 
 
+_SCALE_SAMPLE = 512  # rows mnf_affine_half_grad_scale looks at (csrc/mnf_ahf_bwd_split.hip): rows 0, stride, 2 stride, ...
+
+
+def _rt_layer_scales(lib, run, x: Tensor, buf: Tensor, flat: Tensor, g_last, gl, with_lp: bool, inverse: bool) -> Tensor:
+    """The n gradient scales of a run's ONE gradient launch, entry i for applied layer i: exactly the powers of two the
+    layer-by-layer route computes, one per layer from a sample of that layer's cotangents.  The gradient kernel's results
+    depend on the scale in their last bit, and rows are independent of each other, so the sample rows alone -- at most
+    512 -- are walked through the layers first (grad_x only: n - 1 small ahf_bwd_rt launches) and every layer's scale is
+    taken from them as mnf_affine_half_grad_scale takes it from the whole batch."""
+    n, rows, dim = len(run.layers), x.shape[0], x.shape[1]
+    f0 = run.layers[0]
+    sample = min(rows, _SCALE_SAMPLE)
+    idx = torch.arange(sample, device=x.device) * (rows // sample)
+    xs, outs = x.index_select(0, idx), buf.index_select(1, idx)
+    gls = None if gl is None else gl.index_select(0, idx)
+    g = outs[n - 1] * (-gls).unsqueeze(1) if with_lp else None if g_last is None else g_last.index_select(0, idx)
+    scales = torch.ones(n, dtype=torch.float32, device=x.device)
+    order = list(reversed(run.layers)) if inverse else list(run.layers)
+    n_params = flat.numel() // n
+    for li in range(n - 1, -1, -1):
+        if g is not None or gls is not None:
+            _lib.check("mnf_affine_half_grad_scale", lib.mnf_affine_half_grad_scale(
+                _ptr(g), _ptr(gls), sample, dim, scales[li:].data_ptr(), _stream()))
+        if li == 0:
+            break
+        f = order[li]
+        gx = torch.empty_like(xs)
+        _lib.check("mnf_affine_half_bwd_rt", lib.mnf_affine_half_bwd_rt_det(
+            outs[li - 1].data_ptr(), outs[li].data_ptr(), _ptr(g), _ptr(gls), gx.data_ptr(), None,
+            flat.data_ptr() + 4 * n_params * run.layers.index(f), scales[li:].data_ptr(), sample, dim, int(bool(f.parity)),
+            int(inverse), len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), None, 0, _stream()))
+        g = gx
+    return scales
+
+
 class _AffineRunFn(torch.autograd.Function):
     """A run of equal AffineHalfFlow layers as ONE autograd node: forward = the stack kernel (every
     intermediate written once), backward = the fp32-MFMA gradient kernel layer by layer on the saved
@@ -804,8 +839,21 @@ class _AffineRunFn(torch.autograd.Function):
         home = run._home_now  # (the validated flat home launch_grad decided on for this call)
         ctx.home = home
         flat = home[0].data[home[1]:home[1] + home[2]] if home is not None else flat_with_grad.detach()
-        imgs = run.images(x.device, flat)  # after a weight update: repacked from this one concatenation
         lp = torch.empty(x.shape[0], dtype=torch.float32, device=x.device) if with_lp else None
+        ctx.rt = bool(run._rt_now)
+        if ctx.rt:
+            # the run-time-shaped route (fuse_rt_training): ONE ahf_stack_rt launch that keeps every output in one
+            # (n, rows, dim) buffer -- what the gradient launch reads the layers' inputs and outputs from
+            x = _device_input(x, "input")
+            flat = flat.to(device=x.device, dtype=torch.float32).contiguous()
+            buf = run._launch_rt(x, inverse, ld, False, None, True, (lp, None) if with_lp else None, flat, as_buffer=True)
+            if buf is None or (with_lp and not run.logprob_fused):
+                raise MnfHipError("mnf_affine_half_rt_stack", _lib.MNF_ERR_UNSUPPORTED, "no run-time-shaped run for this shape")
+            ctx.run, ctx.inverse, ctx.with_lp, ctx.n = run, inverse, with_lp, n
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(x, flat, buf)
+            return lp if with_lp else (*buf.unbind(0), ld)
+        imgs = run.images(x.device, flat)  # after a weight update: repacked from this one concatenation
         outs = (run.launch(x, inverse, ld, False, None, keep=True, images=imgs, logprob=(lp, None) if with_lp else None)
                 if imgs[0] is not None else None)
         if outs is None or (with_lp and not run.logprob_fused):
@@ -822,6 +870,8 @@ class _AffineRunFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         run, inverse, n = ctx.run, ctx.inverse, ctx.n
+        if ctx.rt:
+            return _AffineRunFn._backward_rt(ctx, grads)
         x, flat, *mids = ctx.saved_tensors
         z_last = None
         if ctx.with_lp:  # one incoming cotangent: d loss / d log p
@@ -868,6 +918,62 @@ class _AffineRunFn(torch.autograd.Function):
                 gy = None if g is None else g.contiguous()
                 _ahf_layer_backward(lib, f, inputs[li], gy, gl, gx, *args)
             g = gx if li == 0 or grads[li - 1] is None else gx + grads[li - 1]
+        return g, (None if home is not None else grad_flat), None, None, None
+
+
+    @staticmethod
+    def _backward_rt(ctx, grads):
+        """The run-time-shaped route: the layers' gradient scales (_rt_layer_scales) and ONE ahf_bwd_stack_rt launch for the
+        whole run (mnf_affine_half_bwd_rt_stack; its fixed-order form under MNF_DETERMINISTIC=1) -- or, when an INTERMEDIATE of the
+        run carries a cotangent of its own, the layers one by one on the saved outputs, as the layer-by-layer route."""
+        run, inverse, n = ctx.run, ctx.inverse, ctx.n
+        x, flat, buf = ctx.saved_tensors
+        f0, rows, dev = run.layers[0], x.shape[0], x.device
+        if ctx.with_lp:
+            if grads[0] is None:
+                return None, None, None, None, None
+            grads = (None,) * n + (grads[0],)
+        gl = None if grads[-1] is None else grads[-1].contiguous()
+        home = ctx.home
+        want_flat = home is not None or ctx.needs_input_grad[1]
+        grad_flat = (home[0].grad[home[1]:home[1] + home[2]] if home is not None
+                     else torch.zeros_like(flat) if want_flat else None)
+        lib = _lib.load()
+        hid = (len(f0.h_sizes), f0._hid)
+        gx = torch.empty_like(x)
+        one_launch = all(g is None for g in grads[:n - 1])
+        n_ws = 0
+        if one_launch and _lib.deterministic() and grad_flat is not None:
+            n_ws = lib.mnf_affine_half_bwd_rt_stack_det_workspace(rows, f0.dim, *hid, int(f0.scale), int(f0.shift), n)
+            one_launch = n_ws > 0  # (no fixed-order launch for the call: the layers one by one, as they do by themselves)
+        if one_launch:
+            g_last = None if grads[n - 1] is None else grads[n - 1].contiguous()
+            lp_grad, gy, gld = (gl, None, None) if ctx.with_lp else (None, g_last, gl)
+            scale = _rt_layer_scales(lib, run, x, buf, flat, g_last, gl, ctx.with_lp, inverse)
+            work = torch.empty_like(x) if n > 1 else None
+            par = _lib.int_array([int(bool(f.parity)) for f in run.layers])
+            args = (x.data_ptr(), buf.data_ptr(), _ptr(gy), _ptr(lp_grad), _ptr(gld), gx.data_ptr(), _ptr(work),
+                    _ptr(grad_flat), flat.data_ptr(), scale.data_ptr(), par, n, rows, f0.dim, int(inverse), *hid,
+                    int(f0.scale), int(f0.shift))
+            if _lib.deterministic():
+                ws = _rt_det_workspace(n_ws, _ptr(grad_flat), dev)
+                rc = lib.mnf_affine_half_bwd_rt_stack_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
+            else:
+                rc = lib.mnf_affine_half_bwd_rt_stack(*args, _stream())
+            _lib.check("mnf_affine_half_bwd_rt_stack", rc)
+            g = gx
+        else:
+            order = list(reversed(run.layers)) if inverse else list(run.layers)
+            n_params = flat.numel() // n
+            g = grads[n - 1] if not ctx.with_lp else buf[n - 1] * (-gl).unsqueeze(1)
+            for li in range(n - 1, -1, -1):
+                f = order[li]
+                k = run.layers.index(f)
+                gx = torch.empty_like(x)
+                _ahf_layer_backward(lib, f, x if li == 0 else buf[li - 1], None if g is None else g.contiguous(), gl, gx,
+                                    None if grad_flat is None else grad_flat.data_ptr() + 4 * n_params * k,
+                                    flat.data_ptr() + 4 * n_params * k, None, None, None, inverse, y_out=buf[li])
+                g = gx if li == 0 or grads[li - 1] is None else gx + grads[li - 1]
         return g, (None if home is not None else grad_flat), None, None, None
 
 
@@ -2145,6 +2251,10 @@ class _AffineRun:
         self._rt_key = None      # the run-time-shaped route: key and tensor of the concatenated parameters
         self._rt_flat: Tensor | None = None
         self._rt_shape_ok = None  # mnf_affine_half_rt_stack_supported, asked once
+        self._rt_bwd_ok = None    # mnf_affine_half_bwd_rt_stack_supported, asked once
+        self._rt_now = False      # the call in flight trains on the run-time-shaped route (launch_grad -> _AffineRunFn)
+        # the owner's switch (NormalizingFlow / FusedAffineStack .fuse_rt_training), copied here before every pass
+        self.fuse_rt_training = False
 
     @staticmethod
     def compatible(a: "AffineHalfFlow", b: "AffineHalfFlow") -> bool:
@@ -2306,14 +2416,32 @@ class _AffineRun:
     def usable(self, x) -> bool:
         return self.ready(x) is not None
 
+    def _per_shape_trainable(self, device) -> bool:
+        return (not self._unsupported and not any(f.force_generic for f in self.layers)
+                and self.layers[0]._device_index(device) is not None)
+
+    def rt_train_route(self, rows: int, device) -> bool:
+        """``fuse_rt_training``: a training pass of ``rows`` rows goes through one autograd node on the run-time-shaped
+        kernels -- ``rt_route``'s conditions, and the library has the gradient launch for the run too."""
+        if not self.fuse_rt_training or not self.rt_route(rows, device):
+            return False
+        if self._rt_bwd_ok is None:
+            f0 = self.layers[0]
+            self._rt_bwd_ok = bool(_lib.load().mnf_affine_half_bwd_rt_stack_supported(
+                f0.dim, len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), len(self.layers)))
+        return self._rt_bwd_ok
+
     def trainable(self, x) -> bool:
         """Gradients wanted and the whole run can go through one autograd node (stack kernel forward; backward
         layer by layer on the saved intermediates: the fp32-MFMA gradient kernel, or the generic one for shapes
-        it does not cover)."""
-        return (not self._unsupported and isinstance(x, Tensor) and x.is_cuda and x.dim() == 2 and x.shape[0] > 0
-                and x.shape[1] == self.layers[0].dim and not any(f.force_generic for f in self.layers)
-                and any(_wants_grad(f, x) for f in self.layers)
-                and self.layers[0]._device_index(x.device) is not None)
+        it does not cover) -- or, with ``fuse_rt_training`` and a shape without operand image, one
+        ``ahf_stack_rt`` launch forward and one ``ahf_bwd_stack_rt`` launch backward (``rt_train_route``)."""
+        if not (isinstance(x, Tensor) and x.is_cuda and x.dim() == 2 and x.shape[0] > 0
+                and x.shape[1] == self.layers[0].dim and any(_wants_grad(f, x) for f in self.layers)):
+            return False
+        if self._per_shape_trainable(x.device):
+            return True
+        return x.dtype == torch.float32 and self.rt_train_route(x.shape[0], x.device)
 
     def launch_grad(self, x: Tensor, inverse: bool, with_lp: bool = False):
         """(outputs in application order, log_det) with the autograd link; None when the shape has no kernels.
@@ -2324,6 +2452,7 @@ class _AffineRun:
         if with_lp and lp_key in getattr(self, "_lp_unsupported", ()):
             return None
         self._home_now = self.flat_home()
+        self._rt_now = not self._per_shape_trainable(x.device) and self.rt_train_route(x.shape[0], x.device)
         if self._home_now is not None:
             if self._stand_in is None or self._stand_in.device != x.device:
                 self._stand_in = torch.zeros(1, device=x.device, requires_grad=True)
@@ -2342,7 +2471,10 @@ class _AffineRun:
                 refused.add(lp_key)
                 self._lp_unsupported = refused
                 return None
-            self._unsupported = True
+            if self._rt_now:
+                self._rt_bwd_ok = False
+            else:
+                self._unsupported = True
             return None
         if with_lp:
             return out
@@ -2387,9 +2519,9 @@ class _AffineRun:
         _lib.check("mnf_affine_half_stack", rc)
         return list(buf.unbind(0))
 
-    def _launch_rt(self, x, inverse, log_det, accumulate, sqnorm, keep, logprob, flat) -> list[Tensor] | None:
+    def _launch_rt(self, x, inverse, log_det, accumulate, sqnorm, keep, logprob, flat, as_buffer: bool = False):
         """``launch`` on the run-time-shaped kernel: same buffers, the parameters instead of operand images.  Every
-        shape it takes has the log-prob epilogue."""
+        shape it takes has the log-prob epilogue.  ``as_buffer``: the (n, rows, dim) buffer itself, not its planes."""
         f0, n = self.layers[0], len(self.layers)
         x = _device_input(x, "input")
         buf = torch.empty((n if keep else 1, x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
@@ -2404,7 +2536,7 @@ class _AffineRun:
             self._rt_shape_ok, self.logprob_fused = False, False
             return None
         _lib.check("mnf_affine_half_rt_stack", rc)
-        return list(buf.unbind(0))
+        return buf if as_buffer else list(buf.unbind(0))
 
 
 class FusedAffineStack(_TwoWayFlow):
@@ -2432,6 +2564,26 @@ class FusedAffineStack(_TwoWayFlow):
         # not Modules: keep them out of the module tree.  One launch per chunk of at most 32 layers.
         m = _AffineRun.MAX_LAYERS
         self.__dict__["_run_helpers"] = [_AffineRun(layers[k:k + m]) for k in range(0, len(layers), m)]
+        # opt-in, as NormalizingFlow.fuse_rt_training: a shape without per-shape kernels trains as one autograd node per
+        # chunk on the run-time-shaped kernels instead of layer by layer
+        self.fuse_rt_training = False
+
+    def _train_rt(self, x, inverse):
+        """(y, log_det) through one _AffineRunFn node per chunk on the run-time-shaped route, or None."""
+        runs = list(reversed(self._run_helpers)) if inverse else list(self._run_helpers)
+        if not all(r.trainable(x) and not r._per_shape_trainable(x.device) for r in runs):
+            return None
+        y, ld = x, None
+        for k, run in enumerate(runs):
+            res = run.launch_grad(y, inverse)
+            if res is None:  # refused after all: the rest layer by layer from where the pass stands
+                rest = [f for r in runs[k:] for f in (reversed(r.layers) if inverse else r.layers)]
+                for f in rest:
+                    y, l1 = f._run(y, inverse, None)
+                    ld = l1 if ld is None else ld + l1
+                return y, ld
+            y, ld = res[0][-1], (res[1] if ld is None else ld + res[1])
+        return y, ld
 
     def _packed_params(self) -> list[Tensor]:
         return []
@@ -2458,6 +2610,19 @@ class FusedAffineStack(_TwoWayFlow):
 
     def _run(self, x, inverse, accum, sqnorm: Tensor | None = None, overwrite: bool = False):
         runs = list(reversed(self._run_helpers)) if inverse else list(self._run_helpers)
+        for r in runs:  # (the helpers follow the owner's switch on every pass, off as well as on)
+            r.fuse_rt_training = bool(self.fuse_rt_training)
+        if self.fuse_rt_training and sqnorm is None and isinstance(x, Tensor) and any(_wants_grad(f, x) for f in self.layers):
+            res = self._train_rt(x, inverse)
+            if res is not None:
+                y, ld = res
+                if accum is None:
+                    return y, ld
+                if overwrite:
+                    accum.copy_(ld)
+                else:
+                    accum += ld
+                return y, None
         imgs = [r.ready(x) for r in runs]
         if all(i is not None for i in imgs):
             ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
@@ -2561,6 +2726,9 @@ class NormalizingFlow(nn.Module):
         self.layer_event_pick: int | None = None
         # runs of equal AffineHalfFlow layers go out as ONE launch that still writes every intermediate
         self.fuse_affine_runs = True
+        # opt-in: runs WITHOUT per-shape kernels train as one autograd node on the run-time-shaped kernels too (one
+        # ahf_stack_rt launch forward, one ahf_bwd_stack_rt launch backward) instead of one node per layer
+        self.fuse_rt_training = False
         self._last_sqnorm: Tensor | None = None
 
     def invalidate(self) -> None:
@@ -2633,6 +2801,8 @@ class NormalizingFlow(nn.Module):
         while i < n:
             flow = order[i]
             run = run_at.get(i)
+            if isinstance(run, _AffineRun):  # (yields while per-launch event marks are collected, as the no-grad route)
+                run.fuse_rt_training = bool(self.fuse_rt_training) and not events_on
             train_run = run is not None and isinstance(run, _AffineRun) and run.trainable(x)
             run_images = None  # an affine run's validated operand images, handed on to its launch
             if run is not None and not train_run:
@@ -2831,12 +3001,18 @@ class NormalizingFlowModel(NormalizingFlow):
         lp = total = None
         if (std and torch.is_grad_enabled() and not _dispatch.NO_FUSED_LOGPROB and not _NO_RUN_FUSION_ENV
                 and self.fuse_affine_runs and isinstance(x, Tensor) and x.is_cuda and x.dim() == 2
-                and x.shape[0] >= _dispatch.BWD_SPLIT_MIN_ROWS and x.dtype == torch.float32 and self.layer_events is None):
+                and (x.shape[0] >= _dispatch.BWD_SPLIT_MIN_ROWS or (self.fuse_rt_training and x.shape[0] > 0))
+                and x.dtype == torch.float32 and self.layer_events is None):
             # training, the whole model ONE run of AffineHalfFlow layers: one autograd node from x to log p -- the
             # stack kernel's epilogue writes log p, the gradient kernel of the last layer forms -z g itself
             runs = self._affine_runs()
             run = runs.get(0) if len(runs) == 1 else None
-            if isinstance(run, _AffineRun) and len(run.layers) == len(self.flows) and run.trainable(x):
+            if isinstance(run, _AffineRun):
+                run.fuse_rt_training = bool(self.fuse_rt_training)
+            # (per-shape kernels: from BWD_SPLIT_MIN_ROWS rows on, where the split gradient kernel has the lp form; the
+            #  run-time-shaped route -- fuse_rt_training -- has it at every row count it takes)
+            if (isinstance(run, _AffineRun) and len(run.layers) == len(self.flows) and run.trainable(x)
+                    and (x.shape[0] >= _dispatch.BWD_SPLIT_MIN_ROWS or not run._per_shape_trainable(x.device))):
                 lp_fused = run.launch_grad(x, True, with_lp=True)
                 if lp_fused is not None:
                     self._last_sqnorm, self._logprob_done = None, False
