@@ -1,7 +1,9 @@
 """Run by tests/test_rt_deterministic.py in a child process under MNF_DETERMINISTIC=1 (the switch is read once per process):
 the run-time-shaped gradient shapes of tests/test_hip_round6.py land on the *_bwd_rt kernels -- their fixed-order forms --
 and match the float64 oracle; a graphed training step on those kernels replays bit for bit; a gradient pass on the VALU
-kernel (atomic sums) warns once per layer and shape, an rt one does not.  Prints "rt deterministic child ok" at the end."""
+kernel (atomic sums) warns once per layer and shape, an rt one does not; the operating-range table of
+tests/rt_bwd_range_cases.py holds in this mode too, and its `!same` cases repeat bit for bit.  Prints "rt deterministic child
+ok" at the end."""
 import os
 import sys
 import warnings
@@ -15,6 +17,7 @@ for p in (ROOT, HERE, os.path.join(HERE, "golden")):
 import torch  # noqa: E402
 
 import recipes  # noqa: E402
+import rt_bwd_range_cases as R  # noqa: E402
 import torch_mnf_amd as amd  # noqa: E402
 from oracle import flow_oracle as O  # noqa: E402
 from test_hip_autograd import OracleGrads, cot_loss  # noqa: E402
@@ -136,8 +139,26 @@ def warns_once_where_the_sums_are_atomic():
     print("warnings: one for the VALU gradient kernel, none for the rt one")
 
 
+def range_cases_hold_and_repeat():
+    """The table the default mode's test runs (kernel name + oracle budget per case); the cases whose row blocks mix
+    exchange scales (dw_phase_rows' second branch) twice: the same parameter gradients, bit for bit."""
+    twice = 0
+    for case in R.CASES:
+        got = R.run_case(amd, case, prefix="deterministic ")
+        if case.family in ("cot_outlier", "big_hidden"):
+            again, kernel = R.gpu_grads(amd, R.fixture(case))
+            assert kernel == case.layer.kernel, (case.id, kernel)
+            for k in got:
+                if k != "x":
+                    assert torch.equal(got[k].view(torch.int32), again[k].view(torch.int32)), (case.id, k)
+            twice += 1
+    R.run_the_run(amd, prefix="deterministic ")
+    print(f"range: {len(R.CASES)} cases and the one-node run within the oracle budget; {twice} of them twice, bit for bit")
+
+
 if __name__ == "__main__":
     warns_once_where_the_sums_are_atomic()
     graphed_step_replays_identically()
     layers_on_the_rt_kernels()
+    range_cases_hold_and_repeat()
     print("rt deterministic child ok")

@@ -39,12 +39,6 @@ def rt(f):
     return f.to(DEV)
 
 
-def grad_kernel(amd, name):
-    """The gradient kernel family a call is expected on: the run-time-shaped gradient kernels add with float atomics and
-    refuse under MNF_DETERMINISTIC=1 (the suite is also run in that mode), their shapes then take the VALU kernels."""
-    return name.replace("_bwd_rt", "_bwd_generic") if amd.deterministic() else name
-
-
 # ------------------------------------------------------------------ AffineHalfFlow (reference: affine_half_flow.py:28-66)
 AHF_SHAPES = [
     (64, (24, 24), {}), (64, (24, 24, 24), {}), (64, (64, 64, 64), {}), (32, (24, 24), {}), (2, (24, 24), {}),
@@ -280,7 +274,7 @@ def test_affine_half_rt_gradients(amd, O, dim, hs, kw, inverse):
         f.load_state_dict(sd)
         rt(f)
         got = _backward(f, x_cpu, lambda m, x: m.forward(x, inverse=inverse), w_y, w_l)
-        assert amd.last_kernel() == grad_kernel(amd, "ahf_bwd_rt")
+        assert amd.last_kernel() == "ahf_bwd_rt"
         ref.check_all(got, f"ahf_bwd_rt d={dim} h={hs} {kw} rows={rows} inv={inverse}")
 
 
@@ -299,7 +293,7 @@ def test_nsf_cl_rt_gradients(amd, O, dim, K, n_h, inverse):
     f.load_state_dict(sd)
     rt(f)
     got = _backward(f, x_cpu, lambda m, x: (m.inverse if inverse else m.forward)(x), w_y, w_l)
-    assert amd.last_kernel() == grad_kernel(amd, "nsf_bwd_rt")
+    assert amd.last_kernel() == "nsf_bwd_rt"
     ref.check_all(got, f"nsf_bwd_rt ({dim},{K},{n_h}) inv={inverse}")
 
 
@@ -321,7 +315,7 @@ def test_rnvp_rt_gradients(amd, O, dim, hs, seeded):
     ref = OracleGrads(cot_loss(lambda x, p: O.rnvp(x, p, mask.to(x.dtype)), w_y, w_l), z_cpu, sd)
     got = _backward(f, z_cpu, (lambda m, z: m.forward(z, seed=77)) if seeded else (lambda m, z: m.forward(z, mask=mask.to(DEV))),
                     w_y, w_l)
-    assert amd.last_kernel() == grad_kernel(amd, "rnvp_bwd_rt")
+    assert amd.last_kernel() == "rnvp_bwd_rt"
     ref.check_all(got, f"rnvp_bwd_rt d={dim} h={hs} seeded={seeded}")
 
 
@@ -333,7 +327,7 @@ def test_rt_gradients_are_the_default_without_a_specialised_kernel(amd):
              (amd.RNVP(128, h_sizes=(100,)), 128, lambda m, x: m.forward(x, seed=3), "rnvp_bwd_rt", "rnvp_bwd_generic")]
     for f, dim, call, fast, slow in cases:
         f.to(DEV)
-        for rows, want in ((4096, grad_kernel(amd, fast)), (200, slow)):
+        for rows, want in ((4096, fast), (200, slow)):
             x = torch.randn(rows, dim, device=DEV, requires_grad=True)
             f.zero_grad()
             y, ld = call(f, x)
@@ -406,7 +400,7 @@ def test_graphed_training_step_of_a_model_on_the_run_time_shaped_kernels(amd):
         opt_e.step()
         losses_e.append(float(loss.detach()))
     del loss
-    assert kernels <= {"ahf_rt", grad_kernel(amd, "ahf_bwd_rt"), "nsf_rt", grad_kernel(amd, "nsf_bwd_rt")}, kernels
+    assert kernels <= {"ahf_rt", "ahf_bwd_rt", "nsf_rt", "nsf_bwd_rt"}, kernels
     assert losses_e[-1] < losses_e[0]
     model_g, opt_g = build()
     step = amd.GraphedStep(opt_g, lambda x: -model_g.log_prob(x).mean(), batches[0])
@@ -425,7 +419,7 @@ def test_graphed_training_step_of_a_model_on_the_run_time_shaped_kernels(amd):
         x, ld = f.forward(z, seed=9)
         loss = (x.pow(2).mean() - ld.mean())
         loss.backward()
-        assert amd.last_kernel() == grad_kernel(amd, "rnvp_bwd_rt")
+        assert amd.last_kernel() == "rnvp_bwd_rt"
         opt.step()
         first = float(loss.detach()) if first is None else first
     assert float(loss.detach()) < first
@@ -463,7 +457,6 @@ def test_tier_names_the_kernel_that_runs_at_the_envelope_edges(amd, kind, dim, s
     torch.cuda.synchronize()
     k_bwd = amd.last_kernel()
     want_bwd = amd._dispatch.tier(kind, "bwd", rows, dim, hidden, K)
-    if amd.deterministic() and want_bwd == "rt":  # (the *_bwd_rt kernels refuse under MNF_DETERMINISTIC=1)
-        want_bwd = "valu"
+    # (the same under MNF_DETERMINISTIC=1: the *_bwd_rt kernels run in their fixed-order forms there)
     assert amd._dispatch.tier_of_kernel(k_fwd) == amd._dispatch.tier(kind, "fwd", rows, dim, hidden, K), k_fwd
     assert amd._dispatch.tier_of_kernel(k_bwd) == want_bwd, k_bwd
