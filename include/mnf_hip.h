@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 18
+#define MNF_ABI_VERSION 19
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -332,6 +332,14 @@ int mnf_linear_rows(const float* x, const float* W, float* y, int64_t rows, int 
 int64_t mnf_linear_rows_image_floats(int dim);
 int mnf_linear_rows_image_index(int dim, int32_t* idx_host);
 int mnf_linear_rows_img(const float* x, const float* image, float* y, int64_t rows, int dim, void* stream);
+
+/* The same product for ANY 2 <= dim <= 1024 on the fp32 matrix cores (mnf_linear_rows_rt_supported: 1 inside that
+ * range), run-time-shaped: y = x @ M, or y = x @ M^T when trans != 0 (M is read transposed while it is staged:
+ * grad_x = grad_y @ W^T needs no transposed copy).  Every output element is one accumulator over k = 0 .. dim-1 in
+ * ascending order, so y equals mnf_linear_rows' bit for bit (up to the sign of a zero).  x and y must not alias; rows
+ * of any alignment (16-byte aligned pointers and dim % 4 == 0 get 16-byte stores).  Kernel family "linear_rows_rt". */
+int mnf_linear_rows_rt_supported(int dim);
+int mnf_linear_rows_rt(const float* x, const float* M, float* y, int64_t rows, int dim, int trans, void* stream);
 
 /* --------------------------------------------------------- base log-prob epilogue */
 /* log_prob[r] = (log_det ? log_det[r] : 0) - |z_r|^2/2 - dim/2*log(2 pi)   (standard normal base)
@@ -796,6 +804,13 @@ int mnf_rnvp_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host);
 int mnf_affine_const_bwd(const float* x, const float* y, const float* grad_y, const float* s,
                          float* grad_x, float* grad_s, float* grad_t, int64_t rows, int dim,
                          int inverse, void* stream);
+/* The same with grad_s and grad_t summed in a FIXED ORDER (dim <= 256, else MNF_ERR_UNSUPPORTED; both sums wanted): every
+ * workgroup stores its column sums as a block of `workspace`, and the blocks are added in order.  The workspace query
+ * returns the floats needed (0: no fixed-order form for the shape -- the entry above, whose sums are float atomics). */
+int64_t mnf_affine_const_bwd_det_workspace(int64_t rows, int dim);
+int mnf_affine_const_bwd_det(const float* x, const float* y, const float* grad_y, const float* s, float* grad_x,
+                             float* grad_s, float* grad_t, int64_t rows, int dim, int inverse, float* workspace,
+                             int64_t workspace_floats, void* stream);
 /* Glow.inverse followed by ActNormFlow.inverse (torch_mnf/flows/glow.py:33-37, affine_constant_flow.py:22-26: the pair
  * every [ActNormFlow, Glow, NSF_CL] block applies on the way x -> z) as one launch each way, dim = 16, 32 or 64 (else
  * MNF_ERR_UNSUPPORTED): z = (u @ M - t) e^-s with M = W^-1 (dim, dim) row-major and s, t (dim,) as the modules hold
@@ -833,6 +848,16 @@ int mnf_glow_actnorm_inv_logprob_bwd_det(const float* u, const float* grad_log_p
 /* Glow: grad_W (dim, dim) += x^T grad_y   (grad_x is mnf_linear_rows with W^T). */
 int mnf_linear_rows_bwd_weight(const float* x, const float* grad_y, float* grad_W, int64_t rows, int dim,
                                void* stream);
+/* The same sum for any dim mnf_linear_rows_rt_supported has, on the fp32 matrix cores and in a FIXED ORDER in every
+ * mode (no atomics): a wave sums one row slice of one 64 x 64 block of grad_W into `workspace` -- slices of
+ * 16 * ceil(dim / 16) * dim floats each, every element written by exactly one lane -- and the slices are then added to
+ * grad_W in order (more than 32 slices in two steps: 32 partial sums, kept behind the slices, then those).  The slice
+ * count comes from rows, dim and the device's CU count (at most 1024; the workspace is capped at 32 MB).  mnf_linear_rows_bwd_weight_rt_workspace returns the floats the call needs (0 for 0 rows, an
+ * unsupported dim or when no gfx950 device is visible); a smaller workspace is MNF_ERR_INVALID_ARG.  Kernel family
+ * "linear_rows_bwd_weight_rt". */
+int64_t mnf_linear_rows_bwd_weight_rt_workspace(int64_t rows, int dim);
+int mnf_linear_rows_bwd_weight_rt(const float* x, const float* grad_y, float* grad_W, int64_t rows, int dim,
+                                  float* workspace, int64_t workspace_floats, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,6 +35,12 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | not rnvp_bwd_small() | one hidden layer <= 64, padded d >= 64       | rnvp_bwd_mfma                  |
 |                          | >= RT_MIN_ROWS  | 1..4 layers of widths 4..128, any d               | rnvp_bwd_rt                    |
 |                          | else            | anything                                          | rnvp_bwd_generic               |
+| Glow fwd / inv / bwd-x   | any             | d = 16 / 32 / 64 / 128                            | linear_rows_mfma               |
+|                          | >= GLOW_RT_MIN_ROWS | any other 2 <= d <= 1024                      | linear_rows_rt                 |
+|                          | else            | anything                                          | linear_rows_generic (VALU)     |
+| Glow bwd-W               | any             | d = 32                                            | xtg32_mfma_kernel              |
+|                          | >= GLOW_RT_MIN_ROWS | any other 2 <= d <= 1024 (64 and 128 too)     | linear_rows_bwd_weight_rt      |
+|                          | else            | anything                                          | xtg_kernel (VALU, atomics)     |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -85,6 +91,15 @@ RNVP_KEEP_Y_MIN_ROWS = 4096    # the forward pass keeps y = net(mask z) for the 
 RNVP_BWD_GENERIC = False       # measurements: the VALU gradient kernel
 RNVP_BWD_FEW_GRID_OFF = False  # tests: the matrix-core / VALU gradient kernels at every row count
 
+# Glow's row transform x @ W (forward, inverse, grad_x) and its weight gradient x^T g: the run-time-shaped fp32
+# matrix-core kernels (csrc/mnf_linear_mfma.hip: any 2 <= dim <= 1024) take a call without a per-shape kernel from this
+# many rows on -- the smallest of the measured row counts (512 / 2,048 / 8,192 / 65,536 at dim 6, 48, 100, 256) from
+# which they are not slower than the VALU kernels on ALL three passes (tools/time_glow_rt.py, profiles/r9/glow_rt_ab.txt).
+# Forward and grad_x win from 512 rows on (dim 48 at 8,192 rows: 1.3 against 14.6 ns per row); what sets the number is
+# the weight gradient, whose four launches (sums, zero, two reduction steps: ~25 us) lose to the VALU kernel's one at
+# 8,192 rows and dim 6 / 48 (2.9 against 1.3, 3.8 against 1.8 ns per row) and win at 65,536 (0.44 / 0.65, 0.78 / 2.4).
+GLOW_RT_MIN_ROWS = 65536
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -96,6 +111,22 @@ def rnvp_bwd_small(rows: int, dim: int) -> bool:
     if dim >= RNVP_BWD_MFMA_MIN_DIM or rows >= RNVP_BWD_MFMA_ANY_DIM_ROWS:
         return False
     return not (dim >= RNVP_BWD_MFMA_MID_DIM and rows >= RNVP_BWD_MFMA_MID_ROWS)
+
+
+def glow_route(rows: int, dim: int, force_generic: int = 0, weight: bool = False) -> str:
+    """Tier of Glow's x @ W (forward, inverse and grad_x alike; ``weight``: of the weight gradient x^T g).  The kernels
+    are fp32, so an fp32 request changes nothing; force_generic = 1 / 2: the VALU kernels / the run-time-shaped ones at
+    any row count and any dim they support, per-shape dims included."""
+    from . import _lib
+    lib = _lib.load()
+    if force_generic == 1:
+        return "valu"
+    rt = bool(lib.mnf_linear_rows_rt_supported(dim))
+    if force_generic == 2:
+        return "rt" if rt else "valu"
+    if (dim == 32) if weight else lib.mnf_linear_rows_image_floats(dim) > 0:
+        return "per-shape"
+    return "rt" if rt and rows >= GLOW_RT_MIN_ROWS else "valu"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -114,8 +145,11 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
-    "nsf" | "rnvp", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3)."""
+    "nsf" | "rnvp" | "glow", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3; Glow: ();
+    Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's)."""
     from . import _lib
+    if kind == "glow":
+        return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
     if kind == "ahf":
         if direction == "fwd":

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 18  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 19  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -78,6 +78,8 @@ SIGNATURES = {
     "mnf_linear_rows_image_floats": (c_int64, [c_int]),
     "mnf_linear_rows_image_index": (c_int, [c_int, _i32p]),
     "mnf_linear_rows_img": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "mnf_linear_rows_rt_supported": (c_int, [c_int]),
+    "mnf_linear_rows_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "mnf_gauss_logprob": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_gauss_logprob_sq": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_affine_half_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
@@ -158,7 +160,12 @@ SIGNATURES = {
                                       c_void_p, c_int64, c_int, c_int, _intp, c_int, c_void_p, POINTER(c_int), c_void_p]),
     "mnf_affine_const_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_int64, c_int, c_int, c_void_p]),
+    "mnf_affine_const_bwd_det_workspace": (c_int64, [c_int64, c_int]),
+    "mnf_affine_const_bwd_det": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_int, c_int, c_void_p, c_int64, c_void_p]),
     "mnf_linear_rows_bwd_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "mnf_linear_rows_bwd_weight_rt_workspace": (c_int64, [c_int64, c_int]),
+    "mnf_linear_rows_bwd_weight_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "mnf_glow_actnorm_inv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                      c_void_p]),
     "mnf_glow_actnorm_inv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -282,7 +282,10 @@ __global__ void __launch_bounds__(256) affine_const_bwd_fused_kernel(const float
                                                                      const float* __restrict__ s, float* __restrict__ gx,
                                                                      float* __restrict__ grad_s,
                                                                      float* __restrict__ grad_t, int64_t n, int dim,
-                                                                     int inverse) {
+                                                                     int flags) {
+  // flags: bit 0 = inverse; bit 1 = the fixed-order form: grad_s / grad_t are [gridDim.x][dim] blocks of sums, one plain
+  // store per workgroup and column (det_reduce_async adds the blocks in order)
+  const int inverse = flags & 1;
   __shared__ float red_s[256], red_t[256];
   const int col = threadIdx.x % dim;
   const float e = expf(inverse ? -s[col] : s[col]);
@@ -303,8 +306,13 @@ __global__ void __launch_bounds__(256) affine_const_bwd_fused_kernel(const float
       a += red_s[t];
       b += red_t[t];
     }
-    if (grad_s) atomicAdd(grad_s + threadIdx.x, a);
-    if (grad_t) atomicAdd(grad_t + threadIdx.x, b);
+    if (flags & 2) {
+      grad_s[blockIdx.x * dim + threadIdx.x] = a;
+      grad_t[blockIdx.x * dim + threadIdx.x] = b;
+    } else {
+      if (grad_s) atomicAdd(grad_s + threadIdx.x, a);
+      if (grad_t) atomicAdd(grad_t + threadIdx.x, b);
+    }
   }
 }
 
@@ -368,6 +376,34 @@ int mnf_affine_half_bwd(const float* x, const float* grad_y, const float* grad_l
   return check_launch();
 }
 
+// workgroups of the one-pass kernel (dim <= 256): (256 / dim) dim threads each, at most 2048
+static int64_t affine_const_bwd_blocks(int64_t rows, int dim) {
+  const int threads = (256 / dim) * dim;
+  const int64_t blocks = (rows * dim + threads - 1) / threads;
+  return blocks > 2048 ? 2048 : blocks;
+}
+
+int64_t mnf_affine_const_bwd_det_workspace(int64_t rows, int dim) {
+  return rows < 1 || dim < 1 || dim > 256 ? 0 : affine_const_bwd_blocks(rows, dim) * 2 * dim;
+}
+
+int mnf_affine_const_bwd_det(const float* x, const float* y, const float* grad_y, const float* s, float* grad_x,
+                             float* grad_s, float* grad_t, int64_t rows, int dim, int inverse, float* workspace,
+                             int64_t workspace_floats, void* stream) {
+  if (!x || !y || !grad_y || !s || !grad_x || !grad_s || !grad_t || rows < 0 || dim < 1) return MNF_ERR_INVALID_ARG;
+  if (dim > 256) return MNF_ERR_UNSUPPORTED;
+  if (rows == 0) return MNF_OK;
+  const int64_t blocks = affine_const_bwd_blocks(rows, dim);
+  if (!workspace || workspace_floats < blocks * 2 * dim) return MNF_ERR_INVALID_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  float* part_t = workspace + blocks * dim;
+  hipLaunchKernelGGL(affine_const_bwd_fused_kernel, dim3((unsigned)blocks), dim3((256 / dim) * dim), 0, st, x, y, grad_y,
+                     s, grad_x, workspace, part_t, rows * dim, dim, (inverse != 0) | 2);
+  if (int rc = check_launch()) return rc;
+  if (int rc = det_reduce_async(workspace, (int)blocks, dim, dim, grad_s, st)) return rc;
+  return det_reduce_async(part_t, (int)blocks, dim, dim, grad_t, st);
+}
+
 int mnf_affine_const_bwd(const float* x, const float* y, const float* grad_y, const float* s, float* grad_x,
                          float* grad_s, float* grad_t, int64_t rows, int dim, int inverse, void* stream) {
   // forward: y = x e^s + t   -> gx = gy e^s ; gs_j = sum_r gy x e^s = sum_r gy (y - t) ; gt_j = sum_r gy
@@ -381,7 +417,7 @@ int mnf_affine_const_bwd(const float* x, const float* y, const float* grad_y, co
     int64_t blocks = (n + threads - 1) / threads;
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(affine_const_bwd_fused_kernel, dim3((unsigned)blocks), dim3(threads), 0, st, x, y, grad_y, s,
-                       grad_x, grad_s, grad_t, n, dim, inverse != 0);
+                       grad_x, grad_s, grad_t, n, dim, (int)(inverse != 0));
     return check_launch();
   }
   int64_t g = (n + 255) / 256;

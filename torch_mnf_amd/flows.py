@@ -635,9 +635,18 @@ class _AffineConstFn(torch.autograd.Function):
         gy = grad_y.contiguous()
         gx = torch.empty_like(x)
         gs, gt = torch.zeros_like(s), torch.zeros_like(s)
-        _lib.check("mnf_affine_const_bwd", _lib.load().mnf_affine_const_bwd(
-            x.data_ptr(), y.data_ptr(), gy.data_ptr(), s.contiguous().data_ptr(), gx.data_ptr(), gs.data_ptr(),
-            gt.data_ptr(), x.shape[0], x.shape[1], int(ctx.inverse), _stream()))
+        lib = _lib.load()
+        # MNF_DETERMINISTIC=1: the column sums as one block per workgroup, added up in order (dim <= 256)
+        n = lib.mnf_affine_const_bwd_det_workspace(x.shape[0], x.shape[1]) if _lib.deterministic() else 0
+        if n > 0:
+            work = torch.empty(n, dtype=torch.float32, device=x.device)
+            _lib.check("mnf_affine_const_bwd_det", lib.mnf_affine_const_bwd_det(
+                x.data_ptr(), y.data_ptr(), gy.data_ptr(), s.contiguous().data_ptr(), gx.data_ptr(), gs.data_ptr(),
+                gt.data_ptr(), x.shape[0], x.shape[1], int(ctx.inverse), work.data_ptr(), n, _stream()))
+        else:
+            _lib.check("mnf_affine_const_bwd", lib.mnf_affine_const_bwd(
+                x.data_ptr(), y.data_ptr(), gy.data_ptr(), s.contiguous().data_ptr(), gx.data_ptr(), gs.data_ptr(),
+                gt.data_ptr(), x.shape[0], x.shape[1], int(ctx.inverse), _stream()))
         return gx, gs, gt, None
 
 
@@ -660,26 +669,25 @@ def device_drawn_masks():
 _LINEAR_ROWS_INDEX: dict = {}  # (dim, device) -> index table of the MFMA kernel's operand image (None: no such kernel)
 
 
-def _linear_rows(lib, x: Tensor, W: Tensor, y: Tensor) -> None:
-    """y = x @ W for a (dim, dim) W that changes every call (the training path): on the MFMA kernel where dim has one
-    (the operand image is packed from W by one small gather launch), else on the generic kernel."""
-    dim, key = x.shape[1], (x.shape[1], x.device)
-    if key not in _LINEAR_ROWS_INDEX:
-        n = lib.mnf_linear_rows_image_floats(dim)
-        table = None
-        if n > 0:
-            idx = (ctypes.c_int32 * n)()
-            _lib.check("mnf_linear_rows_image_index", lib.mnf_linear_rows_image_index(dim, idx))
-            table = torch.frombuffer(idx, dtype=torch.int32).clone().to(x.device)
-        _LINEAR_ROWS_INDEX[key] = table
-    table = _LINEAR_ROWS_INDEX[key]
+def _linear_rows(lib, x: Tensor, W: Tensor, y: Tensor, force: int = 0, trans: bool = False) -> None:
+    """y = x @ W (x @ W^T when ``trans``) for a (dim, dim) W that changes every call (the training path), by
+    _dispatch.glow_route: on the per-shape MFMA kernel where dim has one (the operand image is packed from W by one small
+    gather launch), on the run-time-shaped one (which reads W transposed itself), else on the VALU kernel."""
+    rows, dim = x.shape
+    route = _dispatch.glow_route(rows, dim, force)
+    if route == "rt":
+        _lib.check("mnf_linear_rows_rt", lib.mnf_linear_rows_rt(x.data_ptr(), W.data_ptr(), y.data_ptr(), rows, dim,
+                                                                int(trans), _stream()))
+        return
+    if trans:
+        W = W.t().contiguous()
+    table = _linear_rows_table(lib, dim, x.device) if route == "per-shape" else None
     if table is None:
-        _lib.check("mnf_linear_rows", lib.mnf_linear_rows(x.data_ptr(), W.data_ptr(), y.data_ptr(), x.shape[0], dim,
-                                                          _stream()))
+        _lib.check("mnf_linear_rows", lib.mnf_linear_rows(x.data_ptr(), W.data_ptr(), y.data_ptr(), rows, dim, _stream()))
         return
     img = _linear_rows_image(lib, W, table)
-    _lib.check("mnf_linear_rows_img", lib.mnf_linear_rows_img(x.data_ptr(), img.data_ptr(), y.data_ptr(), x.shape[0],
-                                                              dim, _stream()))
+    _lib.check("mnf_linear_rows_img", lib.mnf_linear_rows_img(x.data_ptr(), img.data_ptr(), y.data_ptr(), rows, dim,
+                                                              _stream()))
 
 
 def _linear_rows_image(lib, W: Tensor, table: Tensor) -> Tensor:
@@ -763,14 +771,17 @@ class _GlowActNormInvFn(torch.autograd.Function):
 
 
 class _LinearRowsFn(torch.autograd.Function):
-    """y = x @ W with both gradients from the HIP library."""
+    """y = x @ W with both gradients from the HIP library (``force``: the layer's force_generic).  The weight gradient
+    of a shape on the run-time-shaped route is summed in a fixed order through a workspace from torch's allocator (no
+    host synchronisation: the step stays capturable)."""
 
     @staticmethod
-    def forward(ctx, x, W):
+    def forward(ctx, x, W, force=0):
         W = W.contiguous()
         y = torch.empty_like(x)
-        _linear_rows(_lib.load(), x, W, y)
+        _linear_rows(_lib.load(), x, W, y, force)
         ctx.save_for_backward(x, W)
+        ctx.force = force
         return y
 
     @staticmethod
@@ -778,13 +789,19 @@ class _LinearRowsFn(torch.autograd.Function):
         x, W = ctx.saved_tensors
         gy = grad_y.contiguous()
         gx = torch.empty_like(x)
-        Wt = W.t().contiguous()
         lib = _lib.load()
-        _linear_rows(lib, gy, Wt, gx)
+        rows, dim = x.shape
+        _linear_rows(lib, gy, W, gx, ctx.force, trans=True)
         gW = torch.zeros_like(W)
-        _lib.check("mnf_linear_rows_bwd_weight", lib.mnf_linear_rows_bwd_weight(
-            x.data_ptr(), gy.data_ptr(), gW.data_ptr(), x.shape[0], x.shape[1], _stream()))
-        return gx, gW
+        if _dispatch.glow_route(rows, dim, ctx.force, weight=True) == "rt":
+            n = lib.mnf_linear_rows_bwd_weight_rt_workspace(rows, dim)
+            work = torch.empty(n, dtype=torch.float32, device=x.device)
+            _lib.check("mnf_linear_rows_bwd_weight_rt", lib.mnf_linear_rows_bwd_weight_rt(
+                x.data_ptr(), gy.data_ptr(), gW.data_ptr(), rows, dim, work.data_ptr(), n, _stream()))
+        else:
+            _lib.check("mnf_linear_rows_bwd_weight", lib.mnf_linear_rows_bwd_weight(
+                x.data_ptr(), gy.data_ptr(), gW.data_ptr(), rows, dim, _stream()))
+        return gx, gW, None
 
 
 _SCALE_SAMPLE = 512  # rows mnf_affine_half_grad_scale looks at (csrc/mnf_ahf_bwd_split.hip): rows 0, stride, 2 stride, ...
@@ -2059,7 +2076,7 @@ class Glow(_TwoWayFlow):
                 home = _flat_home_of(self, params) if all(p.requires_grad for p in params) else None
                 M, ld = _GlowWeightFn.apply(self.L, self.S, self.U, self._P_on(xg.device).to(torch.float32).contiguous(),
                                             bool(inverse), home)
-                return _LinearRowsFn.apply(xg, M), ld
+                return _LinearRowsFn.apply(xg, M, int(self.force_generic)), ld
             eye = torch.eye(self.dim, device=self.L.device)
             W = self._P_on(self.L.device) @ (torch.tril(self.L, diagonal=-1) + eye) @ (
                 torch.triu(self.U, diagonal=1) + self.S.diag())  # glow.py:20-24, differentiable
@@ -2067,16 +2084,21 @@ class Glow(_TwoWayFlow):
             if inverse:
                 # (inv_ex: torch.inverse's singularity check is a host synchronisation, which a hipGraph capture of the
                 #  training step cannot record; a singular W shows up as inf/nan in the loss either way)
-                return _LinearRowsFn.apply(xg, torch.linalg.inv_ex(W).inverse.to(xg.device)), -ld.to(xg.device)
-            return _LinearRowsFn.apply(xg, W.to(xg.device)), ld.to(xg.device)
+                return (_LinearRowsFn.apply(xg, torch.linalg.inv_ex(W).inverse.to(xg.device), int(self.force_generic)),
+                        -ld.to(xg.device))
+            return _LinearRowsFn.apply(xg, W.to(xg.device), int(self.force_generic)), ld.to(xg.device)
         x = _device_input(x, "input")
         if x.shape[1] != self.dim:
             raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
         W = self._weights(x.device, inverse)
-        img = self._w_image(x.device, inverse)
         y = torch.empty_like(x)
         if x.shape[0] > 0:
-            if img is not None:
+            route = _dispatch.glow_route(x.shape[0], self.dim, int(self.force_generic))
+            img = self._w_image(x.device, inverse) if route == "per-shape" else None
+            if route == "rt":
+                _lib.check("mnf_linear_rows_rt", _lib.load().mnf_linear_rows_rt(
+                    x.data_ptr(), W.data_ptr(), y.data_ptr(), x.shape[0], self.dim, 0, _stream()))
+            elif img is not None:
                 _lib.check("mnf_linear_rows_img", _lib.load().mnf_linear_rows_img(
                     x.data_ptr(), img.data_ptr(), y.data_ptr(), x.shape[0], self.dim, _stream()))
             else:
