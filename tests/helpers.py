@@ -70,6 +70,42 @@ def assert_parity(got, ref32, ref64=None, what: str = "", rtol: float = RTOL, ma
     return err
 
 
+def rowwise_err(a, b) -> float:
+    """max over rows of max_c |a - b| / max_c |b|, over the rows in which b is finite throughout; the finite / non-finite
+    row pattern of a must be b's."""
+    a = np.asarray(a, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    assert a.shape == b.shape and a.ndim == 2, (a.shape, b.shape)
+    fin_a, fin_b = np.isfinite(a).all(axis=1), np.isfinite(b).all(axis=1)
+    assert (fin_a == fin_b).all(), f"finite / non-finite row pattern differs in rows {np.nonzero(fin_a != fin_b)[0][:8].tolist()}"
+    if not fin_b.any():
+        return 0.0
+    a, b = a[fin_b], b[fin_b]
+    return float((np.abs(a - b).max(axis=1) / np.maximum(np.abs(b).max(axis=1), 1e-30)).max())
+
+
+def assert_row_parity(got, ref32, ref64=None, what: str = "", rtol: float = RTOL, max_widening: float | None = MAX_WIDENING):
+    """assert_parity ROW BY ROW, for batches whose rows differ in magnitude by orders (a normwise bound over the whole
+    tensor lets the largest row hide every other): each row's error on its own maximum, the worst row against rtol + twice
+    the same figure between the fp32 and the float64 reference.  Rows in which the fp32 reference is not finite are left
+    out, and ``got`` must be non-finite in exactly those rows.  Recorded in ``PARITY_LOG`` like assert_parity."""
+    if isinstance(got, torch.Tensor):
+        got = got.detach().cpu().numpy()
+    widening = 0.0
+    if ref64 is not None:
+        widening = 2.0 * rowwise_err(np.asarray(ref32), np.asarray(ref64))
+    budget = rtol + widening
+    err = rowwise_err(got, np.asarray(ref32))
+    PARITY_LOG.append({"what": what, "err": err, "budget": budget, "widening": widening,
+                       "widening_share": widening / budget, "used": err / budget, "stress": max_widening is None})
+    if max_widening is not None:
+        assert widening <= max_widening, (f"{what}: the float64 head-room {widening:.3e} exceeds {max_widening:.1e} "
+                                          f"on a fixture that is not a stress case (err {err:.3e})")
+    assert err <= budget, (f"{what}: row-wise error {err:.3e} > budget {budget:.3e} "
+                           f"(= {rtol:.1e} + float64 head-room {widening:.3e})")
+    return err
+
+
 # one record per gradient / optimiser comparison against a float64 oracle (test_hip_autograd.OracleGrads.check,
 # check_vs_float64, budgeted()): what, err, budget, widening -- tests/test_zz_audit.py enforces the 80 % rule on these too
 GRAD_LOG: list[dict] = []

@@ -500,6 +500,11 @@ RUN_DIM, RUN_HS, RUN_LAYERS, RUN_ROWS = 64, (24, 24), 3, 2100
 RUN_OUTLIER_ROW = 1001
 
 
+def run_base_x() -> torch.Tensor:
+    """the run's input rows before any of them is scaled"""
+    return recipes.gaussian(232 + RUN_DIM, RUN_ROWS, RUN_DIM).clone()
+
+
 @functools.lru_cache(maxsize=None)
 def run_fixture():
     """Three (64, (24, 24)) layers of alternating parity at 2,100 rows; the loss -sum_r w_r log p(x_r) with row weights
@@ -509,7 +514,7 @@ def run_fixture():
 
     sds = state_dicts(RUN_DIM, RUN_HS, RUN_LAYERS, {})
     sds = [scaled(sd, {"s_net.0.weight": 1e-4, "t_net.0.weight": 1e-4}) for sd in sds]
-    x = recipes.gaussian(232 + RUN_DIM, RUN_ROWS, RUN_DIM).clone()
+    x = run_base_x()
     big = big_rows_of(RUN_ROWS)
     x[list(big), :RUN_DIM // 2] *= BIG_ROWS
     w = (0.5 + recipes.gaussian(35, RUN_ROWS, 1)[:, 0].abs()) / RUN_ROWS
