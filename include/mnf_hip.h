@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 19
+#define MNF_ABI_VERSION 20
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -845,6 +845,33 @@ int mnf_glow_actnorm_inv_logprob_bwd_det(const float* u, const float* grad_log_p
                                          const float* t, float* grad_u, float* grad_m, float* grad_s, float* grad_t,
                                          float* grad_ld_glow, int64_t rows, int dim, float* workspace,
                                          int64_t workspace_floats, void* stream);
+/* The same pair at ANY 2 <= dim <= 1024, run-time-shaped, on the fp32 matrix cores (torch_mnf/flows/glow.py:33-37,
+ * affine_constant_flow.py:22-26; with log_prob also core.py:46-49).  mnf_glow_actnorm_inv_rt_supported: 1 inside that
+ * range.  One launch forward: z = (u @ M - t) e^-s -- u @ M is mnf_linear_rows_rt's chain (k ascending, one accumulator
+ * per element) and the epilogue is mnf_affine_const's expression, so z equals the layer-by-layer route bit for bit --
+ * and ld_out (1, always written) = ld_glow[0] (NULL: 0) - sum s, summed in a fixed order.  log_det_rows and log_prob
+ * (rows,; both NULL or both set): the pair closes a density pass, log_prob[row] = log_det_rows[row] + ld_out - |z|^2 / 2
+ * - dim log(2 pi) / 2; z may then be NULL (not written).  u and z must not alias; s and t need 4-byte alignment only
+ * (views into a flat parameter buffer); rows of any alignment.  Kernel family "glow_actnorm_inv_rt". */
+int mnf_glow_actnorm_inv_rt_supported(int dim);
+int mnf_glow_actnorm_inv_rt(const float* u, const float* M, const float* s, const float* t, float* z, const float* ld_glow,
+                            float* ld_out, const float* log_det_rows, float* log_prob, int64_t rows, int dim, void* stream);
+/* Its gradients (glow.py:33-37, affine_constant_flow.py:22-26, core.py:46-49 under autograd), from u and the SAVED z (not
+ * recomputed).  Exactly one cotangent is set: grad_z (rows, dim), or grad_log_prob (rows,) of the log-prob form, from
+ * which grad_z = -z grad_log_prob is formed in the kernels.  grad_u = (grad_z e^-s) @ M^T is written (M read transposed,
+ * the layer-by-layer route's bits; must not alias u, z or grad_z); ADDED to are grad_m (dim, dim) = u^T (grad_z e^-s),
+ * grad_s = -sum_r grad_z z - grad_ld[0] (grad_ld: the cotangent of ld_out, or NULL) and grad_t = -sum_r grad_z e^-s
+ * (dim,; either may be NULL) and, in the log-prob form, grad_ld_glow (1, or NULL) = sum_r grad_log_prob[r], which also
+ * enters grad_s as ld_out's cotangent.  Every sum is taken in a FIXED ORDER in every mode (no atomics): one writer per
+ * (row slice, entry) into `workspace`, the slices then added in order as for mnf_linear_rows_bwd_weight_rt.
+ * mnf_glow_actnorm_inv_bwd_rt_workspace returns the floats the call needs (0 for 0 rows, an unsupported dim or when no
+ * gfx950 device is visible); a smaller workspace is MNF_ERR_INVALID_ARG.  Nothing synchronises.  Kernel family
+ * "glow_actnorm_inv_bwd_rt". */
+int64_t mnf_glow_actnorm_inv_bwd_rt_workspace(int64_t rows, int dim);
+int mnf_glow_actnorm_inv_bwd_rt(const float* u, const float* z, const float* grad_z, const float* grad_log_prob,
+                                const float* M, const float* s, const float* t, float* grad_u, float* grad_m, float* grad_s,
+                                float* grad_t, const float* grad_ld, float* grad_ld_glow, int64_t rows, int dim,
+                                float* workspace, int64_t workspace_floats, void* stream);
 /* Glow: grad_W (dim, dim) += x^T grad_y   (grad_x is mnf_linear_rows with W^T). */
 int mnf_linear_rows_bwd_weight(const float* x, const float* grad_y, float* grad_W, int64_t rows, int dim,
                                void* stream);

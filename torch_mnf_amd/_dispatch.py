@@ -41,10 +41,21 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | Glow bwd-W               | any             | d = 32                                            | xtg32_mfma_kernel              |
 |                          | >= GLOW_RT_MIN_ROWS | any other 2 <= d <= 1024 (64 and 128 too)     | linear_rows_bwd_weight_rt      |
 |                          | else            | anything                                          | xtg_kernel (VALU, atomics)     |
+| [Glow, ActNorm].inverse, training fwd | any | d = 16 / 32 / 64                                 | glow_actnorm_inv               |
+|                          | GLOW_ACTNORM_RT (opt-in), where Glow is on linear_rows_rt | other 2 <= d <= 1024 but 128 | glow_actnorm_inv_rt |
+| [Glow, ActNorm].inverse, training bwd | any | d = 16 / 32 / 64                                 | glow_actnorm_inv_bwd           |
+|                          | GLOW_ACTNORM_RT (opt-in), where Glow is on linear_rows_rt | other 2 <= d <= 1024 but 128 | glow_actnorm_inv_bwd_rt |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
 layer, K <= 8 takes n_h <= 64; K = 9 n_h <= 64 at 1-2 layers, 48 at 3-4; K = 10..12 n_h <= 48 / 32; K = 13..16 n_h <= 32.
+
+The [Glow, ActNorm].inverse rows are flows._pair_route: the pair of every [ActNormFlow, Glow, NSF_CL] block on the way
+x -> z with gradients wanted, one autograd node and one launch each way (plus the fixed-order reduction of its sums;
+the rt rows only with GLOW_ACTNORM_RT = True, default False: not yet measured against the layer-by-layer route);
+without gradients, under MNF_NO_PAIR_FUSION=1 or with glow.force_generic = 1 (2 at the per-shape dims) the two layers
+run one after the other as the Glow rows say -- as they do at d = 128, where Glow's product has a per-shape kernel
+(glow_route answers "per-shape") and the pair none: only glow.force_generic = 2 sends that dim to the rt pair.
 
 The ahf_stack_rt row is flows._AffineRun's second route (mnf_affine_half_rt_stack): a run of equal-shaped AffineHalfFlow
 layers without operand image, inside a NormalizingFlow or FusedAffineStack, under wants_rt() for every layer and with no
@@ -99,6 +110,13 @@ RNVP_BWD_FEW_GRID_OFF = False  # tests: the matrix-core / VALU gradient kernels 
 # the weight gradient, whose four launches (sums, zero, two reduction steps: ~25 us) lose to the VALU kernel's one at
 # 8,192 rows and dim 6 / 48 (2.9 against 1.3, 3.8 against 1.8 ns per row) and win at 65,536 (0.44 / 0.65, 0.78 / 2.4).
 GLOW_RT_MIN_ROWS = 65536
+
+# [Glow, ActNorm].inverse as one launch each way on the run-time-shaped kernels (flows._pair_route):
+# OPT-IN.  The fused pair has not been timed against the layer-by-layer route yet (tools/time_glow_actnorm_rt.py writes
+# profiles/r10/glow_actnorm_rt_ab.txt), and every default route in this file rests on a measurement, so the default
+# stays layer by layer; True sends the pair there wherever Glow's own product is on linear_rows_rt.  A layer's
+# force_generic = 2 asks for the run-time-shaped kernels by name and takes the pair either way.
+GLOW_ACTNORM_RT = False
 
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 

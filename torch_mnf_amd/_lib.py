@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 19  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 20  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -166,6 +166,10 @@ SIGNATURES = {
     "mnf_linear_rows_bwd_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_linear_rows_bwd_weight_rt_workspace": (c_int64, [c_int64, c_int]),
     "mnf_linear_rows_bwd_weight_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "mnf_glow_actnorm_inv_rt_supported": (c_int, [c_int]),
+    "mnf_glow_actnorm_inv_rt": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_void_p]),
+    "mnf_glow_actnorm_inv_bwd_rt_workspace": (c_int64, [c_int64, c_int]),
+    "mnf_glow_actnorm_inv_bwd_rt": (c_int, [c_void_p] * 13 + [c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "mnf_glow_actnorm_inv": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                      c_void_p]),
     "mnf_glow_actnorm_inv_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -711,7 +711,7 @@ def _linear_rows_table(lib, dim: int, device) -> Tensor | None:
     return _LINEAR_ROWS_INDEX[key]
 
 
-_PAIR_FUSION_DIMS = (16, 32, 64)  # mnf_glow_actnorm_inv / _bwd (csrc/mnf_glow_actnorm.hip)
+_PAIR_FUSION_DIMS = (16, 32, 64)  # mnf_glow_actnorm_inv / _bwd (csrc/mnf_glow_actnorm.hip); other dims: _pair_route
 _NO_PAIR_FUSION_ENV = os.environ.get("MNF_NO_PAIR_FUSION", "0") == "1"
 # MNF_DETERMINISTIC=1 (read once by the LIBRARY: _lib.deterministic() is the one source of truth): gradient sums through
 # fixed-order two-stage reductions instead of float atomics where a kernel has both (the reference's loop repeats bit for
@@ -730,23 +730,43 @@ def _pair_bwd_workspace(rows: int, dim: int, device):
     return torch.empty(n, dtype=torch.float32, device=device) if n > 0 else None
 
 
+def _pair_bwd_rt(u, z, gz, g_lp, Mc, sc, tc, gu, gM, gs, gt, gl, gld) -> None:
+    """The run-time-shaped pair's gradient launches (mnf_glow_actnorm_inv_bwd_rt): grad_u written, the sums ADDED in a
+    fixed order through a workspace from torch's allocator (no host synchronisation: the step stays capturable)."""
+    lib = _lib.load()
+    rows, dim = u.shape
+    n = lib.mnf_glow_actnorm_inv_bwd_rt_workspace(rows, dim)
+    work = torch.empty(n, dtype=torch.float32, device=u.device)
+    _lib.check("mnf_glow_actnorm_inv_bwd_rt", lib.mnf_glow_actnorm_inv_bwd_rt(
+        u.data_ptr(), z.data_ptr(), _ptr(gz), _ptr(g_lp), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), gu.data_ptr(),
+        gM.data_ptr(), gs.data_ptr(), gt.data_ptr(), _ptr(gl), _ptr(gld), rows, dim, work.data_ptr(), n, _stream()))
+
+
 class _GlowActNormInvFn(torch.autograd.Function):
     """Glow.inverse then ActNormFlow.inverse -- z = (u @ M - t) e^-s, M = W^-1 -- as ONE autograd node with one launch
     each way (glow.py:33-37, affine_constant_flow.py:22-26).  The intermediate u @ M is never written; the gradient
     launch reads u and grad_z once and produces grad_u, grad_M, grad_s and grad_t.  The pair's log|det J| (Glow's, handed
-    in, minus sum s) is a second output of the same launch."""
+    in, minus sum s) is a second output of the same launch.  ``rt``: the run-time-shaped kernels (_pair_route; any dim
+    the library has): z is kept for the gradient launch instead of recomputed, the sums have a fixed order in every mode."""
 
     @staticmethod
-    def forward(ctx, u, M, s, t, ld_glow):
+    def forward(ctx, u, M, s, t, ld_glow, rt=False):
         Mc = M.detach().contiguous()
         sc = s.detach().to(u.device, torch.float32).contiguous()
         tc = t.detach().to(u.device, torch.float32).contiguous()
         z = torch.empty_like(u)
         ld = torch.empty(1, dtype=torch.float32, device=u.device)  # Glow's log|det| - sum s, formed by the launch
-        _lib.check("mnf_glow_actnorm_inv", _lib.load().mnf_glow_actnorm_inv(
-            u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), z.data_ptr(), ld_glow.detach().data_ptr(),
-            ld.data_ptr(), u.shape[0], u.shape[1], _stream()))
-        ctx.save_for_backward(u, Mc, sc, tc)
+        ctx.rt = rt
+        if rt:
+            _lib.check("mnf_glow_actnorm_inv_rt", _lib.load().mnf_glow_actnorm_inv_rt(
+                u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), z.data_ptr(), ld_glow.detach().data_ptr(),
+                ld.data_ptr(), None, None, u.shape[0], u.shape[1], _stream()))
+            ctx.save_for_backward(u, Mc, sc, tc, z)
+        else:
+            _lib.check("mnf_glow_actnorm_inv", _lib.load().mnf_glow_actnorm_inv(
+                u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), z.data_ptr(), ld_glow.detach().data_ptr(),
+                ld.data_ptr(), u.shape[0], u.shape[1], _stream()))
+            ctx.save_for_backward(u, Mc, sc, tc)
         ctx.ld_shape = ld_glow.shape
         ctx.set_materialize_grads(False)
         return z, ld
@@ -754,20 +774,23 @@ class _GlowActNormInvFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_z, grad_ld):
-        u, Mc, sc, tc = ctx.saved_tensors
+        u, Mc, sc, tc = ctx.saved_tensors[:4]
         dim = u.shape[1]
         gz = torch.zeros_like(u) if grad_z is None else grad_z.contiguous()
         gl = None if grad_ld is None else grad_ld.contiguous()
         gu = torch.empty_like(u)
         sums = torch.zeros(dim * dim + 2 * dim, dtype=torch.float32, device=u.device)  # grad_M | grad_s | grad_t
         gM, gs, gt = sums[:dim * dim], sums[dim * dim:dim * dim + dim], sums[dim * dim + dim:]
-        work = _pair_bwd_workspace(u.shape[0], dim, u.device)
-        _lib.check("mnf_glow_actnorm_inv_bwd", _lib.load().mnf_glow_actnorm_inv_bwd_det(
-            u.data_ptr(), gz.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), gu.data_ptr(), gM.data_ptr(),
-            gs.data_ptr(), gt.data_ptr(), _ptr(gl), u.shape[0], dim, _ptr(work), 0 if work is None else work.numel(),
-            _stream()))
+        if ctx.rt:
+            _pair_bwd_rt(u, ctx.saved_tensors[4], gz, None, Mc, sc, tc, gu, gM, gs, gt, gl, None)
+        else:
+            work = _pair_bwd_workspace(u.shape[0], dim, u.device)
+            _lib.check("mnf_glow_actnorm_inv_bwd", _lib.load().mnf_glow_actnorm_inv_bwd_det(
+                u.data_ptr(), gz.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), gu.data_ptr(), gM.data_ptr(),
+                gs.data_ptr(), gt.data_ptr(), _ptr(gl), u.shape[0], dim, _ptr(work), 0 if work is None else work.numel(),
+                _stream()))
         return (gu if ctx.needs_input_grad[0] else None, gM.view(dim, dim), gs.view(sc.shape), gt.view(tc.shape),
-                None if gl is None else gl.reshape(ctx.ld_shape))
+                None if gl is None else gl.reshape(ctx.ld_shape), None)
 
 
 class _LinearRowsFn(torch.autograd.Function):
@@ -2679,45 +2702,73 @@ class FusedAffineStack(_TwoWayFlow):
 class _GlowActNormInvLogProbFn(torch.autograd.Function):
     """The pair closing a density pass under a standard-normal base: log p from (u, the running log_det) in one launch --
     z is not written --, and one gradient launch that forms grad_z = -z d loss / d log p from the recomputed z
-    (mnf_glow_actnorm_inv_logprob / _bwd).  Replaces the pair node + gauss_logprob + the -z g elementwise launch."""
+    (mnf_glow_actnorm_inv_logprob / _bwd).  Replaces the pair node + gauss_logprob + the -z g elementwise launch.
+    ``rt``: the run-time-shaped kernels (_pair_route), which write z once and keep it for the gradient launch."""
 
     @staticmethod
-    def forward(ctx, u, M, s, t, ld_glow, log_det):
+    def forward(ctx, u, M, s, t, ld_glow, log_det, rt=False):
         Mc = M.detach().contiguous()
         sc = s.detach().to(u.device, torch.float32).contiguous()
         tc = t.detach().to(u.device, torch.float32).contiguous()
         lp = torch.empty(u.shape[0], dtype=torch.float32, device=u.device)
-        _lib.check("mnf_glow_actnorm_inv_logprob", _lib.load().mnf_glow_actnorm_inv_logprob(
-            u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), ld_glow.detach().data_ptr(),
-            log_det.detach().contiguous().data_ptr(), lp.data_ptr(), u.shape[0], u.shape[1], _stream()))
-        ctx.save_for_backward(u, Mc, sc, tc)
+        ctx.rt = rt
+        if rt:
+            z = torch.empty_like(u)
+            ld = torch.empty(1, dtype=torch.float32, device=u.device)
+            _lib.check("mnf_glow_actnorm_inv_rt", _lib.load().mnf_glow_actnorm_inv_rt(
+                u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), z.data_ptr(), ld_glow.detach().data_ptr(),
+                ld.data_ptr(), log_det.detach().contiguous().data_ptr(), lp.data_ptr(), u.shape[0], u.shape[1], _stream()))
+            ctx.save_for_backward(u, Mc, sc, tc, z)
+        else:
+            _lib.check("mnf_glow_actnorm_inv_logprob", _lib.load().mnf_glow_actnorm_inv_logprob(
+                u.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), ld_glow.detach().data_ptr(),
+                log_det.detach().contiguous().data_ptr(), lp.data_ptr(), u.shape[0], u.shape[1], _stream()))
+            ctx.save_for_backward(u, Mc, sc, tc)
         ctx.ld_shape = ld_glow.shape
         return lp
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_lp):
-        u, Mc, sc, tc = ctx.saved_tensors
+        u, Mc, sc, tc = ctx.saved_tensors[:4]
         dim = u.shape[1]
         g = grad_lp.contiguous()
         gu = torch.empty_like(u)
         sums = torch.zeros(dim * dim + 2 * dim + 1, dtype=torch.float32, device=u.device)  # grad_M | grad_s | grad_t | grad_ld
         gM, gs = sums[:dim * dim], sums[dim * dim:dim * dim + dim]
         gt, gld = sums[dim * dim + dim:dim * dim + 2 * dim], sums[dim * dim + 2 * dim:]
-        work = _pair_bwd_workspace(u.shape[0], dim, u.device)
-        _lib.check("mnf_glow_actnorm_inv_logprob_bwd", _lib.load().mnf_glow_actnorm_inv_logprob_bwd_det(
-            u.data_ptr(), g.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), gu.data_ptr(), gM.data_ptr(),
-            gs.data_ptr(), gt.data_ptr(), gld.data_ptr(), u.shape[0], dim, _ptr(work), 0 if work is None else work.numel(),
-            _stream()))
+        if ctx.rt:
+            _pair_bwd_rt(u, ctx.saved_tensors[4], None, g, Mc, sc, tc, gu, gM, gs, gt, None, gld)
+        else:
+            work = _pair_bwd_workspace(u.shape[0], dim, u.device)
+            _lib.check("mnf_glow_actnorm_inv_logprob_bwd", _lib.load().mnf_glow_actnorm_inv_logprob_bwd_det(
+                u.data_ptr(), g.data_ptr(), Mc.data_ptr(), sc.data_ptr(), tc.data_ptr(), gu.data_ptr(), gM.data_ptr(),
+                gs.data_ptr(), gt.data_ptr(), gld.data_ptr(), u.shape[0], dim, _ptr(work),
+                0 if work is None else work.numel(), _stream()))
         return (gu if ctx.needs_input_grad[0] else None, gM.view(dim, dim), gs.view(sc.shape), gt.view(tc.shape),
-                gld.reshape(ctx.ld_shape), g)
+                gld.reshape(ctx.ld_shape), g, None)
+
+
+def _pair_route(glow: "Glow", rows: int) -> str | None:
+    """Which kernels the fused pair has for this Glow layer and row count: "per-shape" (dim 16 / 32 / 64, no
+    force_generic), "rt" (any other dim the library has, where Glow's own product is on the run-time-shaped kernels by
+    _dispatch.glow_route: from GLOW_RT_MIN_ROWS rows on under the opt-in _dispatch.GLOW_ACTNORM_RT, or
+    force_generic == 2), or None: layer by layer."""
+    force = int(glow.force_generic)
+    if glow.dim in _PAIR_FUSION_DIMS:
+        return None if force else "per-shape"
+    if force == 1 or (force != 2 and not _dispatch.GLOW_ACTNORM_RT):
+        return None
+    if not _lib.load().mnf_glow_actnorm_inv_rt_supported(glow.dim):
+        return None
+    return "rt" if _dispatch.glow_route(rows, glow.dim, force) == "rt" else None
 
 
 def _pair_fusable(glow: "Glow", actnorm: "ActNormFlow", x) -> bool:
     """Training pass, x -> z: can Glow.inverse + ActNormFlow.inverse at this input go out as the fused pair?"""
     return (not _NO_PAIR_FUSION_ENV and isinstance(x, Tensor) and x.is_cuda and x.dim() == 2 and x.shape[0] > 0
-            and x.dtype == torch.float32 and glow.dim == actnorm.dim == x.shape[1] and glow.dim in _PAIR_FUSION_DIMS
-            and actnorm.data_dep_init_done is not False and not glow.force_generic
+            and x.dtype == torch.float32 and glow.dim == actnorm.dim == x.shape[1]
+            and _pair_route(glow, x.shape[0]) is not None and actnorm.data_dep_init_done is not False
             and glow.L.is_cuda and glow.L.device == x.device and glow.L.dtype == torch.float32
             and _wants_grad(glow, x) and _wants_grad(actnorm, x))
 
@@ -2725,13 +2776,21 @@ def _pair_fusable(glow: "Glow", actnorm: "ActNormFlow", x) -> bool:
 def _glow_actnorm_inverse(glow: "Glow", actnorm: "ActNormFlow", x: Tensor, log_det: Tensor | None = None):
     """(z, the pair's log|det J|); with ``log_det`` (rows,): log p under a standard-normal base instead (one tensor)."""
     xg = _grad_input(x)
-    params = [glow.L, glow.S, glow.U]
-    home = _flat_home_of(glow, params) if all(p.requires_grad for p in params) else None
-    M, ld_glow = _GlowWeightFn.apply(glow.L, glow.S, glow.U, glow._P_on(xg.device).to(torch.float32).contiguous(), True,
-                                     home)
+    if glow.dim <= _GLOW_WEIGHT_MAX_DIM:
+        params = [glow.L, glow.S, glow.U]
+        home = _flat_home_of(glow, params) if all(p.requires_grad for p in params) else None
+        M, ld_glow = _GlowWeightFn.apply(glow.L, glow.S, glow.U, glow._P_on(xg.device).to(torch.float32).contiguous(),
+                                         True, home)
+    else:  # (beyond mnf_glow_weight's dims: W^-1 and log|det| through torch, differentiable, as Glow._run does)
+        eye = torch.eye(glow.dim, device=glow.L.device)
+        W = glow._P_on(glow.L.device) @ (torch.tril(glow.L, diagonal=-1) + eye) @ (
+            torch.triu(glow.U, diagonal=1) + glow.S.diag())  # glow.py:20-24
+        M = torch.linalg.inv_ex(W).inverse  # (inv_ex: no host synchronisation, the step stays capturable)
+        ld_glow = -glow.S.abs().log().sum()
+    rt = _pair_route(glow, xg.shape[0]) == "rt"
     if log_det is not None:
-        return _GlowActNormInvLogProbFn.apply(xg, M, actnorm.s.to(xg.device), actnorm.t.to(xg.device), ld_glow, log_det)
-    return _GlowActNormInvFn.apply(xg, M, actnorm.s.to(xg.device), actnorm.t.to(xg.device), ld_glow)
+        return _GlowActNormInvLogProbFn.apply(xg, M, actnorm.s.to(xg.device), actnorm.t.to(xg.device), ld_glow, log_det, rt)
+    return _GlowActNormInvFn.apply(xg, M, actnorm.s.to(xg.device), actnorm.t.to(xg.device), ld_glow, rt)
 
 
 class NormalizingFlow(nn.Module):
