@@ -2,8 +2,8 @@
 the run-time-shaped gradient shapes of tests/test_hip_round6.py land on the *_bwd_rt kernels -- their fixed-order forms --
 and match the float64 oracle; a graphed training step on those kernels replays bit for bit; a gradient pass on the VALU
 kernel (atomic sums) warns once per layer and shape, an rt one does not; the operating-range table of
-tests/rt_bwd_range_cases.py holds in this mode too, and its `!same` cases repeat bit for bit.  Prints "rt deterministic child
-ok" at the end."""
+tests/rt_bwd_range_cases.py holds in this mode too, and its `!same` cases repeat bit for bit; so does the gradient half of the
+parameter-range table (tests/rt_param_range_cases.py).  Prints "rt deterministic child ok" at the end."""
 import os
 import sys
 import warnings
@@ -18,6 +18,7 @@ import torch  # noqa: E402
 
 import recipes  # noqa: E402
 import rt_bwd_range_cases as R  # noqa: E402
+import rt_param_range_cases as P  # noqa: E402
 import torch_mnf_amd as amd  # noqa: E402
 from oracle import flow_oracle as O  # noqa: E402
 from test_hip_autograd import OracleGrads, cot_loss  # noqa: E402
@@ -156,9 +157,17 @@ def range_cases_hold_and_repeat():
     print(f"range: {len(R.CASES)} cases and the one-node run within the oracle budget; {twice} of them twice, bit for bit")
 
 
+def parameter_range_cases_hold():
+    """The gradient half of tests/rt_param_range_cases.py on the fixed-order kernels: kernel name + oracle budget per case."""
+    for case in P.GRAD_CASES:
+        P.run_gradients(amd, case, prefix="deterministic ")
+    print(f"parameter range: {len(P.GRAD_CASES)} gradient cases within the oracle budget")
+
+
 if __name__ == "__main__":
     warns_once_where_the_sums_are_atomic()
     graphed_step_replays_identically()
     layers_on_the_rt_kernels()
     range_cases_hold_and_repeat()
+    parameter_range_cases_hold()
     print("rt deterministic child ok")

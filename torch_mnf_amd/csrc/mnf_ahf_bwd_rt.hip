@@ -107,7 +107,9 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
     // row's addresses, which another wave of this workgroup writes), and so are its last reads of the exchange area and
     // the weight stream; block_weight_max's two barriers then keep this layer's staging behind them as well.
     if (i != a.n_layers - 1) __syncthreads();
-    const float wmax = block_weight_max(ly.flat, a.n_params, scratch);
+    float wmx = net_weight_max(ly.flat, a.s_net, 0.f);  // (one net only: s_net and t_net are the same descriptor)
+    if (a.has_scale && a.has_shift) wmx = net_weight_max(ly.flat, a.t_net, wmx);
+    const float wmax = block_weight_max(wmx, scratch);
     const int we = weight_exponent(wmax);
     const float wup = pow2f(we);
     src.wdown = pow2f(-we);

@@ -251,7 +251,9 @@ __global__ void __launch_bounds__(NW * 64) ahf_rt_kernel(AhfRtArgs a) {
     ly.parity = (a.parity >> l) & 1u;
     ly.accumulate = i > 0 || a.accumulate;
     // (the two barriers in here also keep this layer's staging behind the other waves' last reads of the previous one's)
-    const float wmax = rt::block_weight_max(ly.flat, a.n_params, scratch);
+    float wmx = rt::net_weight_max(ly.flat, a.s_net, 0.f);  // (one net only: s_net and t_net are the same descriptor)
+    if (a.has_scale && a.has_shift) wmx = rt::net_weight_max(ly.flat, a.t_net, wmx);
+    const float wmax = rt::block_weight_max(wmx, scratch);
     const int e = rt::weight_exponent(wmax);  // weights are staged as w 2^-e: the largest one just below 2^15
     const float wup = rt::pow2f(e);
     src.wdown = rt::pow2f(-e);

@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(512) nsf_bwd_rt_kernel(NsfBwdRtArgs a) {
   uint32_t* blocks = rt_lds + kBwdHeadWords;
   float* bias = reinterpret_cast<float*>(blocks + a.block_words);
   const BwdLds lds = bwd_lds(rt_lds, bias + a.bias_words, a.ht_tiles, a.dt_tiles, a.ct_tiles);
-  const float wmax = block_weight_max(a.flat, a.n_params, scratch);
+  const float wmax = block_weight_max(net_weight_max(a.flat, a.f2, net_weight_max(a.flat, a.f1, 0.f)), scratch);
   const int we = weight_exponent(wmax);
   const float wup = pow2f(we);
   Source<false> src{blocks, bias, a.cb, a.bt, 0, 0, 0, pow2f(-we), 0};

@@ -178,7 +178,7 @@ __global__ void __launch_bounds__(NW * 64) nsf_rt_kernel(NsfRtArgs a) {
   float* scratch = reinterpret_cast<float*>(rt_lds);
   uint32_t* blocks = rt_lds + 16;
   float* bias = reinterpret_cast<float*>(blocks + a.block_words);
-  const float wmax = rt::block_weight_max(a.flat, a.n_params, scratch);
+  const float wmax = rt::block_weight_max(rt::net_weight_max(a.flat, a.f2, rt::net_weight_max(a.flat, a.f1, 0.f)), scratch);
   const int e = rt::weight_exponent(wmax);
   const float wup = rt::pow2f(e);
   rt::Source<RESIDENT> src{blocks, bias, a.cb, a.bt, 0, 0, 0, rt::pow2f(-e), 0};

@@ -56,7 +56,10 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
   uint32_t* blocks = rt_lds + kBwdHeadWords;
   float* bias = reinterpret_cast<float*>(blocks + a.block_words);
   const BwdLds lds = bwd_lds(rt_lds, bias + a.bias_words, a.ht_tiles, a.dt_tiles, a.ct_tiles);
-  const float wmax = block_weight_max(a.flat, a.n_params, scratch);
+  const int head_floats = a.net.sizes[a.net.n_lin] * a.dim;  // t and s: Linear(h_n, dim) each
+  float wmx = net_weight_max(a.flat, a.net, 0.f);
+  wmx = range_abs_max(a.flat + a.s_w, head_floats, range_abs_max(a.flat + a.t_w, head_floats, wmx));
+  const float wmax = block_weight_max(wmx, scratch);
   const int we = weight_exponent(wmax);
   const float wup = pow2f(we);
   Source<false> src{blocks, bias, a.cb, a.bt, 0, 0, 0, pow2f(-we), 0};
@@ -69,6 +72,7 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
   const int ht_last = exH_tile_of(nd, n_hid);
   const int64_t n_blocks = (a.rows + 16 * nw - 1) / (16 * nw);
   float* const gflat = a.grad_flat + blockIdx.x * a.slot_floats;
+  float* const sC2 = lds.sH + (kMaxBwdLayers + 1) * 8;  // (the head's spare 8 floats) scales of the scale-head cotangent tiles
 
   for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
     const int64_t r = blk * (16 * nw) + 16 * wave + j;
@@ -129,13 +133,22 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
           store4(gzrow, col, d, VEC, live, gz);
         }
       }
-      // dW_t, dW_s, db_t, db_s of the two tiles: cotangent tiles [t0 t1 s0 s1] x last hidden vector
+      // dW_t, dW_s, db_t, db_s of the two tiles: cotangent tiles [t0 t1 s0 s1] x last hidden vector.  The shift and the
+      // scale cotangents get an exchange scale EACH: g_s carries the factor (a1 - shift), so a large shift (a head bias of
+      // 2^36) would otherwise push g_t, which does not depend on it, down to f16's subnormals
       if (gflat) {
-        f32x4 cv[MT_MAX];
+        f32x4 ct[MT_MAX], cs[MT_MAX];
 #pragma unroll
-        for (int m = 0; m < MT_MAX; ++m) cv[m] = m < 2 ? gt2[m & 1] : m < 4 ? gs2[m & 1] : f32x4{0.f, 0.f, 0.f, 0.f};
-        const float sc = exchange_store<MT_MAX>(cv, 4, lds.exC, 0, 16 * wave, lane, lds.ident);
-        if (lane == 0) lds.sC[wave] = sc;
+        for (int m = 0; m < MT_MAX; ++m) {
+          ct[m] = m < 2 ? gt2[m & 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+          cs[m] = m < 2 ? gs2[m & 1] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const float sct = exchange_store<MT_MAX>(ct, 2, lds.exC, 0, 16 * wave, lane, lds.ident);
+        const float scs = exchange_store<MT_MAX>(cs, 2, lds.exC, 2, 16 * wave, lane, lds.ident);
+        if (lane == 0) {
+          lds.sC[wave] = sct;
+          sC2[wave] = scs;
+        }
       }
       // the chain's first step: accd += W_t^T-blocks x [g_t tiles] + W_s^T-blocks x [g_s tiles]
       uint32_t* bufT = src.cur_blocks();
@@ -170,7 +183,7 @@ __global__ void __launch_bounds__(512) rnvp_bwd_rt_kernel(RnvpBwdRtArgs a) {
       }
       if (gflat) {
         dw_phase(lds.exC, 0, mo, lds.exH, ht_last, MTh, lds.sC, lds.sH + n_hid * 8, nw, inv_gs, gflat + a.t_w, gflat + a.t_b, d, hl, m0, 0);
-        dw_phase(lds.exC, 2, mo, lds.exH, ht_last, MTh, lds.sC, lds.sH + n_hid * 8, nw, inv_gs, gflat + a.s_w, gflat + a.s_b, d, hl, m0, 0);
+        dw_phase(lds.exC, 2, mo, lds.exH, ht_last, MTh, sC2, lds.sH + n_hid * 8, nw, inv_gs, gflat + a.s_w, gflat + a.s_b, d, hl, m0, 0);
       }
     }
     // ---- hidden layers backwards (y has no activation: derivative 1), then the first layer: grad_z += mask * W_0^T delta_1

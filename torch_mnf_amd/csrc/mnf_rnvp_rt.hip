@@ -130,7 +130,10 @@ __global__ void __launch_bounds__(NW * 64) rnvp_rt_kernel(RnvpRtArgs a) {
   float* scratch = reinterpret_cast<float*>(rt_lds);
   uint32_t* blocks = rt_lds + 16;
   float* bias = reinterpret_cast<float*>(blocks + a.block_words);
-  const float wmax = rt::block_weight_max(a.flat, a.n_params, scratch);
+  const int head_floats = a.net.sizes[a.net.n_lin] * a.dim;  // t and s: Linear(h_n, dim) each
+  float wmx = rt::net_weight_max(a.flat, a.net, 0.f);
+  wmx = rt::range_abs_max(a.flat + a.s_w, head_floats, rt::range_abs_max(a.flat + a.t_w, head_floats, wmx));
+  const float wmax = rt::block_weight_max(wmx, scratch);
   const int e = rt::weight_exponent(wmax);
   const float wup = rt::pow2f(e);
   rt::Source<RESIDENT> src{blocks, bias, a.cb, a.bt, 0, 0, 0, rt::pow2f(-e), 0};

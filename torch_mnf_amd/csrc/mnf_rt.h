@@ -14,9 +14,18 @@
 //   * the first layer streams its input from memory K-step by K-step (any width), the last one streams its output tiles
 //     to the layer's epilogue (any width);
 //   * range: instead of recomputing out-of-range tiles on an fp32 path, a row whose operands reach the split limit is
-//     scaled by a power of two before the split and its products scaled back (exact), and weights beyond the limit are
-//     staged scaled down by a power of two -- results do not depend on the input or weight range.  Rows holding
-//     non-finite values give NaN (the reference: inf or NaN).
+//     scaled by a power of two before the split and its products scaled back (exact), and every weight of the layer is
+//     staged as w 2^-e, ONE e per launch, the largest finite weight just below 2^15.  Rows holding non-finite values
+//     give NaN (the reference: inf or NaN).  The envelope inside which results carry fp32's precision (split operands
+//     below 2^-14 are carried to 2^-36 absolute, mnf_split.h; tests/rt_param_range_cases.py, profiles/r11/):
+//       - biases: any finite value -- they are staged as plain fp32, added after the products are scaled back, and the
+//         scan for e does not look at them;
+//       - a Linear whose largest weight is 2^-k of the launch's largest is staged below 2^(15-k): at k = 27 that is
+//         2^-12 and a product's error 2^-36 / 2^-12 = 2^-24 relative, fp32's own; beyond it the error doubles per bit
+//         (1e-5 near k = 34).  Per-Linear maxima within 2^27 of each other are safe; one e per Linear is not done;
+//       - a hidden vector is scaled per ROW: a unit of magnitude A >= 2^13 brings its neighbours v to ~v 2^13 / A, carried
+//         to A 2^-49 / |v| relative: fp32 grade up to A ~ 2^25 |v|, 1e-5 at ~2^32;
+//       - a non-finite weight is left out of the maximum; the outputs it feeds are non-finite, the others do not notice.
 //
 // Three size classes are instantiated per layer type (MT_MAX = 4 / 8 / 16 hidden tiles: widths <= 64 / 128 / 256).
 #pragma once
@@ -42,8 +51,10 @@ typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// weight range: max |w| over the finite entries of the parameter vector, by every workgroup for itself (the vector is
-// L2-resident; a pass costs microseconds), and the power of two that brings it to <= kSplitWeightLimit
+// weight range: max |w| over the finite WEIGHTS of the layer's nets (heads included), by every workgroup for itself (the
+// vector is L2-resident; a pass costs microseconds), and the power of two that brings it to just below 2^15.  Biases are
+// not looked at: they are staged as plain fp32 (stage_bias) and added after the products are scaled back, so a large one
+// must not push the weights towards f16's subnormals.
 // ---------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float finite_abs(float v) {
   const float a = __builtin_fabsf(v);
@@ -56,10 +67,19 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
-// scratch: >= 16 floats of LDS; ends with a barrier; every thread returns the same value
-__device__ __forceinline__ float block_weight_max(const float* __restrict__ flat, int n, float* scratch) {
-  float mx = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) mx = __builtin_fmaxf(mx, finite_abs(flat[i]));
+// this thread's share of max |w| over n floats / over the weight matrices of every Linear of a net
+__device__ __forceinline__ float range_abs_max(const float* __restrict__ w, int n, float mx) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) mx = __builtin_fmaxf(mx, finite_abs(w[i]));
+  return mx;
+}
+__device__ __forceinline__ float net_weight_max(const float* __restrict__ flat, const NetDesc& nd, float mx) {
+  for (int l = 0; l < nd.n_lin; ++l) mx = range_abs_max(flat + nd.w_off[l], nd.sizes[l] * nd.sizes[l + 1], mx);
+  return mx;
+}
+
+// mx: the thread's share (range_abs_max / net_weight_max over every weight range of the layer).  scratch: >= 16 floats of
+// LDS; ends with a barrier; every thread returns the same value
+__device__ __forceinline__ float block_weight_max(float mx, float* scratch) {
   mx = wave_max(mx);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = mx;
   __syncthreads();

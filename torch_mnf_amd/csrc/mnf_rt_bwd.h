@@ -199,6 +199,15 @@ struct NoBias {
   __device__ __forceinline__ float operator()(int, int) const { return 0.f; }
 };
 
+// value > 0 of one element of a split tile (half `odd` of the packed words): the sign of the head part -- of the residual
+// where the head is +0: a positive unit whose row was scaled down far enough (a neighbour of 2^24) rounds to a zero head
+// and would be taken for a negative one (slope 0.2 for 1)
+__device__ __forceinline__ bool split_positive(uint32_t hi_word, uint32_t lo_word, int odd) {
+  const uint32_t hh = (hi_word >> (16 * odd)) & 0xffffu, hl = (lo_word >> (16 * odd)) & 0xffffu;
+  const uint32_t half = hh != 0u ? hh : hl;
+  return half != 0u && (half & 0x8000u) == 0u;
+}
+
 // the LeakyReLU derivative of a hidden vector from its (split) values: sign of the head part, per unit
 template <int MT_MAX>
 __device__ __forceinline__ void leaky_gate(const Hidden<MT_MAX, 1>& h, f32x4 (&g)[MT_MAX]) {
@@ -207,9 +216,7 @@ __device__ __forceinline__ void leaky_gate(const Hidden<MT_MAX, 1>& h, f32x4 (&g
     // packed f16 pairs: element r of the tile sits in half (r & 1) of word (r >> 1); positive <=> sign bit clear and non-zero
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const uint32_t half = (h.hi[0][m][r >> 1] >> (16 * (r & 1))) & 0xffffu;
-      const bool pos = half != 0u && (half & 0x8000u) == 0u;
-      g[m][r] = pos ? 1.f : kLeakySlope;
+      g[m][r] = split_positive(h.hi[0][m][r >> 1], h.lo[0][m][r >> 1], r & 1) ? 1.f : kLeakySlope;
     }
   }
 }
@@ -224,8 +231,7 @@ __device__ __forceinline__ uint32_t pack_signs(const Hidden<MT_MAX, 1>& h) {
   for (int m = 0; m < MT_MAX; ++m)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const uint32_t half = (h.hi[0][m][r >> 1] >> (16 * (r & 1))) & 0xffffu;
-      bits |= (half != 0u && (half & 0x8000u) == 0u) ? 1u << (4 * m + r) : 0u;  // LeakyReLU keeps the sign
+      bits |= split_positive(h.hi[0][m][r >> 1], h.lo[0][m][r >> 1], r & 1) ? 1u << (4 * m + r) : 0u;  // LeakyReLU keeps the sign
     }
   return bits;
 }
