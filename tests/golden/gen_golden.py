@@ -6,7 +6,8 @@ Run in the build container only (needs /root/reference; it never travels):
 
 Every fixture is data: inputs, masks/noise, the reference's outputs, and -- where they
 cannot be rebuilt from ``recipes.py`` -- parameter values.  No reference source text is
-stored.  Fixture list follows SURVEY.md section 8c (G1..G9); G10 adds the shapes the kernels run padded.
+stored.  Fixture list follows SURVEY.md section 8c (G1..G9); G10 adds the shapes the kernels run padded;
+G17 the reference's own autograd gradients for the shapes of the run-time-shaped tier (cases: g17_cases.py).
 """
 from __future__ import annotations
 
@@ -617,6 +618,99 @@ def g15_maf_iaf():
     save("g15_maf_iaf", **out)
 
 
+# ----------------------------------------------------------------------------- G17
+def g17_rt_grads():
+    """The reference's OWN autograd gradients (fp32, and its .double() run rounded to fp32) for the cases of
+    g17_cases.py: single AffineHalfFlow / NSF_CL / RNVP / Glow layers under sum(y * w_y) + sum(log_det * w_l), a 4-layer
+    AffineHalfFlow run and one [ActNormFlow, Glow, NSF_CL] block under -mean log p.  Inputs, loss weights, masks and
+    parameters are recipe draws, rebuilt by the tests: the files hold ``{tag}.grad.{name}``, ``{tag}.grad64.{name}`` and
+    the two loss values ``{tag}.loss`` / ``{tag}.loss64`` only.  One file per entry of g17_cases.PARTS."""
+    import g17_cases as C
+
+    def build(tag, dt):
+        kind, p = C.kind_of(tag), C.params(tag)
+        spec = C.KINDS[kind][tag]
+
+        def cast(sd):
+            return {k: v.to(dt) for k, v in sd.items()}
+
+        def glow(gp, dim):
+            gl = nf.Glow(dim).to(dt)
+            gl.P = gp["P"].to(dt)
+            gl.load_state_dict(cast({k: gp[k] for k in ("L", "S", "U")}))
+            return gl
+
+        if kind == "ahf":
+            dim, hs, kw, parity, _ = spec
+            m = nf.AffineHalfFlow(dim, parity, h_sizes=hs, **kw).to(dt)
+            m.load_state_dict(cast(p))
+        elif kind == "nsf":
+            dim, K, n_h, _ = spec
+            m = nf.NSF_CL(dim, K=K, B=3, n_h=n_h).to(dt)
+            m.load_state_dict(cast(p))
+        elif kind == "rnvp":
+            dim, hs = spec
+            m = nf.RNVP(dim, h_sizes=hs).to(dt)
+            m.load_state_dict(cast(p))
+        elif kind == "glow":
+            m = glow(p, spec[0])
+        elif kind == "run":
+            dim, hs, n = spec
+            flows = []
+            for i, sd in enumerate(p):
+                f = nf.AffineHalfFlow(dim, bool(i % 2), h_sizes=hs).to(dt)
+                f.load_state_dict(cast(sd))
+                flows.append(f)
+            m = nf.NormalizingFlowModel(MultivariateNormal(torch.zeros(dim, dtype=dt), torch.eye(dim, dtype=dt)), flows)
+        else:
+            dim, K, n_h = spec
+            an = nf.ActNormFlow(dim).to(dt)
+            an.load_state_dict(cast(p[0]))
+            an.data_dep_init_done = True
+            sp = nf.NSF_CL(dim, K=K, B=3, n_h=n_h).to(dt)
+            sp.load_state_dict(cast(p[2]))
+            m = nf.NormalizingFlowModel(MultivariateNormal(torch.zeros(dim, dtype=dt), torch.eye(dim, dtype=dt)),
+                                        [an, glow(p[1], dim), sp])
+        return m
+
+    def run(tag, dt):
+        kind, inp = C.kind_of(tag), C.inputs(tag)
+        m = build(tag, dt)
+        x = inp["x"].to(dt).requires_grad_(True)
+        if kind in ("run", "block"):
+            zs, ld = m.inverse(x)
+            loss = -(m.base.log_prob(zs[-1]) + ld).mean()
+        else:
+            if kind == "rnvp":  # the layer draws its mask itself: hand it the recipe's
+                real_bernoulli = torch.bernoulli
+                torch.bernoulli = lambda t, *a, **k: inp["mask"].to(t.dtype)
+                try:
+                    y, ld = m.forward(x)
+                finally:
+                    torch.bernoulli = real_bernoulli
+            else:
+                inverse = C.KINDS[kind][tag][-1]
+                y, ld = m.inverse(x) if inverse else m.forward(x)
+            loss = (y * inp["w_y"].to(dt)).sum() + (ld * inp["w_l"].to(dt)).sum()
+        loss.backward()
+        grads = {"x": x.grad, **{k: q.grad for k, q in m.named_parameters()}}
+        assert list(grads) == C.grad_names(tag), (tag, list(grads), C.grad_names(tag))
+        assert all(g is not None and bool(torch.isfinite(g).all()) for g in grads.values()), tag
+        return loss.detach(), grads
+
+    for name, kinds in C.PARTS.items():
+        out = {}
+        for kind in kinds:
+            for tag in C.KINDS[kind]:
+                loss32, g32 = run(tag, torch.float32)
+                loss64, g64 = run(tag, torch.float64)
+                out[f"{tag}.loss"], out[f"{tag}.loss64"] = np.float32(loss32.item()), np.float64(loss64.item())
+                for k in g32:
+                    out[f"{tag}.grad.{k}"] = npy(g32[k])
+                    out[f"{tag}.grad64.{k}"] = npy(g64[k]).astype(np.float32)
+        save(name, **out)
+
+
 # ----------------------------------------------------------------------------- G9
 def g9_logdet_shapes():
     x = recipes.gaussian(900, 8, 4)
@@ -658,4 +752,5 @@ if __name__ == "__main__":
     g14_mnf_linear_kl()
     g15_maf_iaf()
     g16_mnf_linear_wide()
+    g17_rt_grads()
     g9_logdet_shapes()

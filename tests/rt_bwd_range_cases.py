@@ -27,7 +27,7 @@ import torch
 import recipes
 from oracle import flow_oracle as O
 from test_hip_autograd import GBASE, GBASE_STRESS, OracleGrads, check_vs_float64
-from test_hip_round6 import _rnvp_sd
+from recipes import rnvp_params_layers as _rnvp_sd
 
 DEV = "cuda"
 LIMIT = 2.0 ** 13   # mnf_rt.h kSplitLimit; down_exponent(v, 13) is 0 below it

@@ -3,7 +3,8 @@ the run-time-shaped gradient shapes of tests/test_hip_round6.py land on the *_bw
 and match the float64 oracle; a graphed training step on those kernels replays bit for bit; a gradient pass on the VALU
 kernel (atomic sums) warns once per layer and shape, an rt one does not; the operating-range table of
 tests/rt_bwd_range_cases.py holds in this mode too, and its `!same` cases repeat bit for bit; so does the gradient half of the
-parameter-range table (tests/rt_param_range_cases.py).  Prints "rt deterministic child ok" at the end."""
+parameter-range table (tests/rt_param_range_cases.py); the reference's own gradients (fixture G17) of the AffineHalfFlow d = 64
+case and of the 4-layer run hold on the fixed-order kernels with the same budget.  Prints "rt deterministic child ok" at the end."""
 import os
 import sys
 import warnings
@@ -16,13 +17,17 @@ for p in (ROOT, HERE, os.path.join(HERE, "golden")):
 
 import torch  # noqa: E402
 
+import numpy as np  # noqa: E402
+
 import recipes  # noqa: E402
 import rt_bwd_range_cases as R  # noqa: E402
+import rt_golden_cases as G  # noqa: E402
 import rt_param_range_cases as P  # noqa: E402
 import torch_mnf_amd as amd  # noqa: E402
 from oracle import flow_oracle as O  # noqa: E402
 from test_hip_autograd import OracleGrads, cot_loss  # noqa: E402
-from test_hip_round6 import AHF_BWD_SHAPES, NSF_BWD_SHAPES, RNVP_BWD_SHAPES, _backward, _rnvp_sd  # noqa: E402
+from recipes import rnvp_params_layers as _rnvp_sd  # noqa: E402
+from test_hip_round6 import AHF_BWD_SHAPES, NSF_BWD_SHAPES, RNVP_BWD_SHAPES, _backward  # noqa: E402
 
 DEV = "cuda"
 assert amd.deterministic(), "run under MNF_DETERMINISTIC=1"
@@ -164,10 +169,27 @@ def parameter_range_cases_hold():
     print(f"parameter range: {len(P.GRAD_CASES)} gradient cases within the oracle budget")
 
 
+def reference_gradients_hold():
+    """Fixture G17 (tests/golden/g17_cases.py) in this mode: the AffineHalfFlow d = 64 case on ahf_bwd_rt, the 4-layer run
+    layer by layer and as one node (ahf_bwd_stack_rt) -- tests/test_hip_rt_golden.py's checks, the same budget."""
+    cache = {}
+
+    def golden(name):
+        if name not in cache:
+            cache[name] = dict(np.load(os.path.join(HERE, "golden", name + ".npz")))
+        return cache[name]
+
+    G.layer_case(amd, golden, "ahf_d64_h24x24_inv", 2, prefix="deterministic ")
+    for fused in (False, True):
+        G.run_case(amd, golden, fused, prefix="deterministic ")
+    print("reference gradients: the d = 64 layer and the 4-layer run (both routes) within the fixture's budget")
+
+
 if __name__ == "__main__":
     warns_once_where_the_sums_are_atomic()
     graphed_step_replays_identically()
     layers_on_the_rt_kernels()
     range_cases_hold_and_repeat()
     parameter_range_cases_hold()
+    reference_gradients_hold()
     print("rt deterministic child ok")

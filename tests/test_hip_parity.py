@@ -49,17 +49,27 @@ def ahf_module(amd, sd, dim, parity, kernel="split", **kw):
     return select_kernel(f.to(DEV), kernel)
 
 
-KERNELS = ["split", "fp32", "generic"]  # f16 hi+lo MFMA (default) / fp32 MFMA / shape-generic
+# f16 hi+lo MFMA (default) / fp32 MFMA / shape-generic (VALU) / run-time-shaped matrix-core kernels (csrc/mnf_rt.h)
+KERNELS = ["split", "fp32", "generic", "rt"]
+KERNEL_IDS = ["split", "fp32", "generic", "tier_rt"]  # (`-k _rt` selects every reference fixture on the rt tier)
+RT_FAMILY = {"AffineHalfFlow": "ahf_rt", "NSF_CL": "nsf_rt", "RNVP": "rnvp_rt"}
 
 
 def select_kernel(f, kernel):
-    f.force_generic = kernel == "generic"
+    f.force_generic = 2 if kernel == "rt" else kernel == "generic"
     f.force_fp32_mfma = kernel == "fp32"
     return f
 
 
+def ran_on(amd, f, kernel):
+    """After a call of layer ``f``: on "rt" the launch must have been the run-time-shaped kernel of the layer's kind (a
+    shape the tier lacks would be served by the VALU kernel without a word)."""
+    if kernel == "rt":
+        assert amd.last_kernel() == RT_FAMILY[type(f).__name__], (type(f).__name__, amd.last_kernel())
+
+
 # ------------------------------------------------------------------ AffineHalfFlow
-@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("kernel", KERNELS, ids=KERNEL_IDS)
 @pytest.mark.parametrize("dim", [64, 256])
 @pytest.mark.parametrize("parity", [False, True])
 def test_g2_affine_half_golden(amd, golden, dim, parity, kernel):
@@ -68,12 +78,15 @@ def test_g2_affine_half_golden(amd, golden, dim, parity, kernel):
     f = ahf_module(amd, recipes.affine_half_params(200 + dim + int(parity), dim), dim, parity, kernel)
     z = cuda(fx[f"{tag}.z"])
     x, ld = f.forward(z)
+    ran_on(amd, f, kernel)
     assert_close(x, fx[f"{tag}.fwd"], RTOL, "fwd")
     assert_close(ld, fx[f"{tag}.ld_fwd"], RTOL, "ld_fwd")
     x, ld = f.inverse(z)
+    ran_on(amd, f, kernel)
     assert_close(x, fx[f"{tag}.inv"], RTOL, "inv")
     assert_close(ld, fx[f"{tag}.ld_inv"], RTOL, "ld_inv")
     x2, ld2 = f.forward(z, inverse=True)  # the reference's extra keyword (:44)
+    ran_on(amd, f, kernel)
     assert torch.equal(x, x2) and torch.equal(ld, ld2)
 
 
@@ -93,14 +106,26 @@ def test_mfma_kernel_is_selected(amd):
     assert lib.mnf_affine_half_image_floats(258, 3, hid, 1, 1) == 0
 
 
-@pytest.mark.parametrize("tag,kw", [("nice", dict(scale=False)), ("noshift", dict(shift=False)),
-                                    ("h2", dict(h_sizes=(16, 40))), ("h1", dict(h_sizes=(7,)))])
+G2_VARIANTS = [("nice", dict(scale=False)), ("noshift", dict(shift=False)), ("h2", dict(h_sizes=(16, 40))), ("h1", dict(h_sizes=(7,)))]
+
+
+@pytest.mark.parametrize("tag,kw", G2_VARIANTS)
 def test_g2_affine_half_variants(amd, golden, tag, kw):
+    g2_variant(amd, golden, tag, kw, "split")
+
+
+@pytest.mark.parametrize("tag,kw", G2_VARIANTS, ids=[v[0] for v in G2_VARIANTS])
+def test_g2_affine_half_variants_rt(amd, golden, tag, kw):
+    g2_variant(amd, golden, tag, kw, "rt")
+
+
+def g2_variant(amd, golden, tag, kw, kernel):
     fx = golden("g2_affine_half_single")
-    f = ahf_module(amd, recipes.affine_half_params(290, 10, **kw), 10, True, **kw)
+    f = ahf_module(amd, recipes.affine_half_params(290, 10, **kw), 10, True, kernel, **kw)
     z = cuda(fx[f"{tag}.z"])
     for name, fn in (("fwd", f.forward), ("inv", f.inverse)):
         x, ld = fn(z)
+        ran_on(amd, f, kernel)
         assert_close(x, fx[f"{tag}.{name}"], RTOL, f"{tag}.{name}")
         assert_close(ld, fx[f"{tag}.ld_{name}"], RTOL, f"{tag}.ld_{name}")
 
@@ -761,7 +786,7 @@ def test_rqs_all_outside_is_identity_and_too_many_bins_raises(amd):
 
 @pytest.mark.parametrize("cfg", [(32, 8, 8, 1.0), (32, 8, 16, 1.0), (2, 8, 16, 1.0), (6, 5, 8, 1.0),
                                  (32, 8, 8, 2.0), (2, 8, 16, 2.0)])
-@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("kernel", KERNELS, ids=KERNEL_IDS)
 def test_g5_nsf_cl_layer(amd, golden, cfg, kernel):
     dim, K, n_h, gain = cfg
     fx = golden("g5_nsf_cl_layer")
@@ -769,11 +794,12 @@ def test_g5_nsf_cl_layer(amd, golden, cfg, kernel):
     f = amd.NSF_CL(dim, K=K, B=3, n_h=n_h)
     f.load_state_dict(recipes.nsf_cl_params(500 + dim + n_h, dim, K, n_h, gain=gain))
     f = select_kernel(f.to(DEV), kernel)
-    if dim == 32 and kernel != "generic":
+    if dim == 32 and kernel not in ("generic", "rt"):
         assert (f._split_image(torch.device(DEV, 0)) is not None) == (kernel == "split")
     z = cuda(fx[f"{tag}.z"])
     for name, fn in (("fwd", f.forward), ("inv", f.inverse)):
         x, ld = fn(z)
+        ran_on(amd, f, kernel)
         if gain == 1.0:  # nn.Linear-scale weights: the plain 1e-5 rule
             assert_close(x, fx[f"{tag}.{name}"], RTOL, f"{tag}.{name}")
             assert_close(ld, fx[f"{tag}.ld_{name}"], RTOL, f"{tag}.ld_{name}")
@@ -949,34 +975,41 @@ def test_glow_and_actnorm_layers_vs_oracle(amd, O, dim):
 
 # --------------------------------------------------------------------------- RNVP
 @pytest.mark.parametrize("dim", [50, 800, 784])
-@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("kernel", KERNELS, ids=KERNEL_IDS)
 def test_g7_rnvp(amd, golden, dim, kernel):
     fx = golden("g7_rnvp")
     f = amd.RNVP(dim, h_sizes=(50,))
     f.load_state_dict(recipes.rnvp_params(700 + dim, dim, 50))
     f = select_kernel(f.to(DEV), kernel)
-    if dim >= 64 and kernel != "generic":
+    if dim >= 64 and kernel not in ("generic", "rt"):
         assert (f._split_image(torch.device(DEV, 0)) is not None) == (kernel == "split")
     z = cuda(fx[f"d{dim}.z"])
     mask = unpack_mask(fx[f"d{dim}.mask_bits"], dim).to(DEV)
     x, ld = f.forward(z, mask=mask)
+    ran_on(amd, f, kernel)
     assert_close(x, fx[f"d{dim}.x"], RTOL, "x")
     assert_close(ld, fx[f"d{dim}.ld"], RTOL, "ld")
     assert not hasattr(f, "inverse")
     # without a mask argument a Bernoulli(0.5) mask is drawn per element per call
     x1, _ = f.forward(z)
+    ran_on(amd, f, kernel)
     x2, _ = f.forward(z)
+    ran_on(amd, f, kernel)
     assert not torch.equal(x1, x2)
     # ... from the library's counter-based generator: reproducible under torch.manual_seed, and a
     # seeded call equals an explicit-mask call with the mask mask_for() reports
     torch.manual_seed(5)
     xa, lda = f.forward(z)
+    ran_on(amd, f, kernel)
     torch.manual_seed(5)
     xb, ldb = f.forward(z)
+    ran_on(amd, f, kernel)
     assert torch.equal(xa, xb) and torch.equal(lda, ldb)
     xs, lds = f.forward(z, seed=1234)
+    ran_on(amd, f, kernel)
     m = f.mask_for(1234, z.shape[0])
     xm, ldm = f.forward(z, mask=m)
+    ran_on(amd, f, kernel)
     # (the in-kernel-mask path evaluates the same formula in its binary-mask form,
     #  x = (1 - gate) t + (m ? z : gate z), so the two agree to rounding, not bit for bit)
     assert_close(xs, xm, 1e-6, "seeded vs explicit mask x")
@@ -1282,13 +1315,24 @@ def test_affine_half_any_three_hidden_widths_up_to_32(amd, O, dim, h_sizes, kern
 def test_g10_padded_shapes_vs_reference(amd, golden):
     """Reference-generated fixture for the shapes the kernels run padded: AffineHalfFlow with narrow halves, odd hidden
     widths or an absent net, RNVP with dim % 16 != 0 / other hidden widths -- every one on an MFMA kernel."""
+    g10_padded_shapes(amd, golden, "split")
+
+
+def test_g10_padded_shapes_vs_reference_rt(amd, golden):
+    """The same fixture with every layer on the run-time-shaped kernel (every width there is >= 4)."""
+    g10_padded_shapes(amd, golden, "rt")
+
+
+def g10_padded_shapes(amd, golden, kernel):
     fx = golden("g10_padded_shapes")
     for k, (tag, (dim, kw)) in enumerate(recipes.G10_AHF.items()):
-        f = ahf_module(amd, recipes.affine_half_params(1000 + 10 * k, dim, s_last_gain=2.0, **kw), dim, bool(k % 2), **kw)
-        assert f._split_image(torch.device(DEV, 0)) is not None, tag
+        f = ahf_module(amd, recipes.affine_half_params(1000 + 10 * k, dim, s_last_gain=2.0, **kw), dim, bool(k % 2), kernel, **kw)
+        if kernel != "rt":
+            assert f._split_image(torch.device(DEV, 0)) is not None, tag
         z = cuda(fx[f"ahf.{tag}.z"])
         for name, fn in (("fwd", f.forward), ("inv", f.inverse)):
             y, ld = fn(z)
+            ran_on(amd, f, kernel)
             assert_close(y, fx[f"ahf.{tag}.{name}"], RTOL, f"{tag}.{name}")
             if kw.get("scale", True):
                 assert_close(ld, fx[f"ahf.{tag}.ld_{name}"], RTOL, f"{tag}.ld_{name}")
@@ -1297,9 +1341,11 @@ def test_g10_padded_shapes_vs_reference(amd, golden):
     for k, (tag, (dim, hid)) in enumerate(recipes.G10_RNVP.items()):
         f = amd.RNVP(dim, h_sizes=(hid,))
         f.load_state_dict(recipes.rnvp_params(1100 + 10 * k, dim, hid))
-        f.to(DEV)
-        assert f._split_image(torch.device(DEV, 0)) is not None, tag
+        select_kernel(f.to(DEV), kernel)
+        if kernel != "rt":
+            assert f._split_image(torch.device(DEV, 0)) is not None, tag
         x, ld = f.forward(cuda(fx[f"rnvp.{tag}.z"]), mask=unpack_mask(fx[f"rnvp.{tag}.mask_bits"], dim).to(DEV))
+        ran_on(amd, f, kernel)
         assert_close(x, fx[f"rnvp.{tag}.x"], RTOL, f"{tag}.x")
         assert_close(ld, fx[f"rnvp.{tag}.ld"], RTOL, f"{tag}.ld")
 

@@ -185,14 +185,7 @@ def test_nsf_cl_rt_round_trip_and_default(amd):
 
 
 # ------------------------------------------------------------------ RNVP (reference: rnvp.py:19-39)
-def _rnvp_sd(seed, dim, hs):
-    rng = np.random.default_rng(seed)
-    sd = recipes.mlp_params(rng, "net", (dim, *hs), gain=1.5)
-    k = 1.5 / np.sqrt(hs[-1])
-    for name in ("t", "s"):
-        sd[f"{name}.weight"] = torch.from_numpy(rng.uniform(-k, k, size=(dim, hs[-1])).astype(np.float32))
-        sd[f"{name}.bias"] = torch.from_numpy(rng.uniform(-k, k, size=(dim,)).astype(np.float32))
-    return sd
+_rnvp_sd = recipes.rnvp_params_layers  # (seed, dim, h_sizes): any number of conditioner layers
 
 
 RNVP_SHAPES = [(800, (100,)), (50, (100,)), (128, (30,)), (784, (50, 40)), (50, (17,)), (37, (200,)), (1024, (64, 64)),

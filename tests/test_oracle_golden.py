@@ -397,3 +397,27 @@ def test_g15_maf_iaf(golden, tag, parity):
         spec = {"kind": "iaf", "params": g15_params(tag, parity), "masks": masks, "parity": parity}
         y_iaf, ld_iaf = O.apply_layer(spec, x, not inverse)
         assert torch.equal(y_iaf, y) and torch.equal(ld_iaf, ld)
+
+
+# ------------------------------------------------------------------ G17: the reference's own autograd gradients
+import g17_cases as G17  # noqa: E402
+import rt_golden_cases as RG  # noqa: E402
+
+
+@pytest.mark.parametrize("tag", G17.all_tags())
+def test_g17_oracle_gradients_are_the_references(golden, tag):
+    """Every gradient test of the suite is refereed by torch.autograd through the oracle's restatement of the layers:
+    here that referee meets the reference's own autograd, in fp32 against its fp32 gradients and in float64 against its
+    .double() run, for x and every parameter -- the project rule (1e-5 normwise plus twice the fixture's own
+    fp32-vs-fp64 distance, which assert_parity caps at MAX_WIDENING for every case)."""
+    g32, g64, loss32, loss64 = RG.fixture_grads(golden, tag)
+    o_loss32, o32 = RG.oracle_grads(tag, torch.float32)
+    o_loss64, o64 = RG.oracle_grads(tag, torch.float64)
+    assert abs(o_loss32 - loss32) <= 1e-5 * abs(loss32) and abs(o_loss64 - loss64) <= 1e-5 * abs(loss64)
+    for k in G17.grad_names(tag):
+        ref32, ref64 = g32[k].numpy(), g64[k].numpy()
+        assert float(np.abs(ref64).max()) > 0, f"{tag}: the fixture's gradient {k} is all zero"
+        e32 = assert_parity(o32[k], ref32, ref64, f"g17 {tag} fp32 oracle grad {k}")
+        # (the float64 gradients are stored rounded to fp32: 6e-8 of the 1e-5)
+        e64 = assert_parity(o64[k], ref64, None, f"g17 {tag} float64 oracle grad {k}")
+        print(f"g17 {tag} grad {k}: fp32 oracle vs fp32 reference {e32:.2e}, float64 vs float64 {e64:.2e}")

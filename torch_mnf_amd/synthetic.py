@@ -78,6 +78,18 @@ def rnvp_params(seed: int, dim: int, h: int, gain: float = 1.5) -> dict:
     return sd
 
 
+def rnvp_params_layers(seed: int, dim: int, h_sizes, gain: float = 1.5) -> dict:
+    """flows.RNVP state_dict for any number of conditioner layers: net = MLP(dim, *h_sizes); t, s = Linear(h_sizes[-1], dim)
+    with weight and bias drawn from U(-gain / sqrt(h_sizes[-1]), gain / sqrt(h_sizes[-1])), weight first."""
+    rng = np.random.default_rng(seed)
+    sd = mlp_params(rng, "net", (dim, *h_sizes), gain=gain)
+    k = gain / np.sqrt(h_sizes[-1])
+    for name in ("t", "s"):
+        sd[f"{name}.weight"] = torch.from_numpy(rng.uniform(-k, k, size=(dim, h_sizes[-1])).astype(np.float32))
+        sd[f"{name}.bias"] = torch.from_numpy(rng.uniform(-k, k, size=(dim,)).astype(np.float32))
+    return sd
+
+
 def maf_params(seed: int, dim: int, h_sizes=(24, 24, 24), gain: float = 1.0, last_gain: float = 1.0) -> dict:
     """flows.MAF / IAF state_dict WITHOUT the mask buffers: net = MADE(dim, h_sizes, 2 dim) -> net.{2l}.weight / .bias
     (the masks are the deterministic construction of layers/made.py and stay what the constructor built)."""
