@@ -259,7 +259,9 @@ int mnf_rnvp(const float* z, const float* mask, float* x, float* log_det, int ac
 /* Same layer with the mask generated inside the kernel when mask == NULL: element (r, j) is bit
  * (j & 31) of a 32-bit hash of (seed, r, j >> 5) -- a stateless Bernoulli(0.5) stream owned by
  * this library.  mnf_rnvp_mask writes exactly that mask as floats, so a
- * seeded call can be reproduced with an explicit mask (and by the CPU oracle). */
+ * seeded call can be reproduced with an explicit mask, and on the CPU: tests/rng_reference.py restates
+ * the hash (and the two normal streams, mnf_mnf_linear_noise / mnf_sample_z0_noise) in numpy, and
+ * tests/test_hip_rng.py holds the device to it. */
 int mnf_rnvp_seeded(const float* z, const float* mask, uint64_t seed, float* x, float* log_det,
                     int accumulate, const float* flat, const float* image, const void* split_image,
                     int64_t rows, int dim, int n_hidden, const int* hidden_host,
