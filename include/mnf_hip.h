@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 20
+#define MNF_ABI_VERSION 21
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -436,6 +436,35 @@ int mnf_maf(const float* x, float* y, float* log_det, int accumulate, const floa
 int mnf_maf_bwd(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
                 const float* flat, const uint8_t* masks, int64_t rows, int dim, int parity, int sequential, int n_hidden,
                 const int* hidden_host, void* stream);
+/* The ONE-PASS direction (sequential = 0: MAF.inverse, IAF.forward) on the f16 matrix pipe (mnf_maf_rt.hip,
+ * mnf_maf_bwd_rt.hip: run-time layer count and widths, weights read from `flat` under `masks`; no operand image): same
+ * flat / masks / parity / log_det conventions as mnf_maf.  A masked-out weight is staged as exactly 0 by a select (an inf
+ * or NaN parked there stays out), does not set the launch's staging exponent, and its grad_flat entry receives no add.
+ *   mnf_maf_rt        >= 1 hidden layer of widths 4 .. 128, any dim >= 1; rows of any alignment (16-byte row accesses
+ *                     where dim % 4 == 0 and x, y are aligned, else element by element)
+ *   mnf_maf_bwd_rt    1 .. 4 hidden layers of widths 4 .. 64, any dim whose exchange area fits 160 KB of LDS with at least
+ *                     one wave.  grad_scale_dev: device float, a power of two that brings the cotangents near 1
+ *                     (mnf_affine_half_grad_scale).  grad_x is written, grad_flat ADDED to with float atomics (or NULL);
+ *                     grad_y / grad_ld may be NULL.  Refuses (MNF_ERR_UNSUPPORTED) when MNF_DETERMINISTIC is set.
+ *   mnf_maf_bwd_rt_det / _det_workspace   fixed-order sums: as mnf_affine_half_bwd_rt_det.
+ * The *_supported queries are host only and are the launchers' own plans.  MNF_ERR_INVALID_ARG (before any launch): a NULL
+ * x / y / grad_x / flat / masks / grad_scale_dev, x == y, x == grad_x, grad_y == grad_x, grad_flat == flat, rows < 0,
+ * dim < 1, n_hidden < 1, a NULL or non-positive hidden.  rows == 0: MNF_OK, nothing is launched.  A shape outside the
+ * limits: MNF_ERR_UNSUPPORTED (the caller runs mnf_maf / mnf_maf_bwd). */
+int mnf_maf_rt_supported(int dim, int n_hidden, const int* hidden_host);
+int mnf_maf_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host);
+/* Workgroups of the mnf_maf_rt launch of `rows` rows (a persistent grid: workgroup b takes the blocks of 128 rows b,
+ * b + grid, ...); 0: nothing to launch, a shape outside the plan, or no gfx950 device visible. */
+int64_t mnf_maf_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden_host);
+int mnf_maf_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
+               int64_t rows, int dim, int parity, int n_hidden, const int* hidden_host, void* stream);
+int mnf_maf_bwd_rt(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                   const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim, int parity,
+                   int n_hidden, const int* hidden_host, void* stream);
+int64_t mnf_maf_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host);
+int mnf_maf_bwd_rt_det(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                       const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim, int parity,
+                       int n_hidden, const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
 
 /* ------------------------------------------------ MNFLinear.forward behind the flow path
  * torch_mnf/layers/mnf_linear.py:46-56 with z (rows, n_in) = what sample_z's last flow wrote:
@@ -795,7 +824,9 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  *                                     K = 9 n_h <= 64 (1 - 2 layers) / 48 (3 - 4); K = 10 .. 12 n_h <= 48 / 32;
  *                                     K = 13 .. 16 n_h <= 32
  *   mnf_rnvp_rt_supported             >= 1 conditioner layer, widths 4 .. 256, any dim
- *   mnf_rnvp_bwd_rt_supported         1 .. 4 conditioner layers of widths 4 .. 128, any dim */
+ *   mnf_rnvp_bwd_rt_supported         1 .. 4 conditioner layers of widths 4 .. 128, any dim
+ *   mnf_maf_rt_supported              (declared with mnf_maf_rt) >= 1 hidden layer, widths 4 .. 128, any dim
+ *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim */
 int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);

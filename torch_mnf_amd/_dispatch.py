@@ -45,6 +45,11 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | GLOW_ACTNORM_RT (opt-in), where Glow is on linear_rows_rt | other 2 <= d <= 1024 but 128 | glow_actnorm_inv_rt |
 | [Glow, ActNorm].inverse, training bwd | any | d = 16 / 32 / 64                                 | glow_actnorm_inv_bwd           |
 |                          | GLOW_ACTNORM_RT (opt-in), where Glow is on linear_rows_rt | other 2 <= d <= 1024 but 128 | glow_actnorm_inv_bwd_rt |
+| MAF.inverse / IAF.forward fwd | >= MAF_RT_MIN_ROWS | >= 1 hidden layer of widths 4..128, any d     | maf_rt                         |
+|                          | else            | anything                                          | maf_generic (VALU)             |
+| MAF.inverse / IAF.forward bwd | >= MAF_RT_MIN_ROWS | 1..4 hidden layers of widths 4..64, any d     | maf_bwd_rt                     |
+|                          | else            | anything                                          | maf_bwd_generic (VALU, atomics) |
+| MAF.forward / IAF.inverse, both passes | any | anything (element by element)                    | maf_generic / maf_bwd_generic  |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -118,6 +123,17 @@ GLOW_RT_MIN_ROWS = 65536
 # force_generic = 2 asks for the run-time-shaped kernels by name and takes the pair either way.
 GLOW_ACTNORM_RT = False
 
+# MAF / IAF, the one-pass direction (MAF.inverse, IAF.forward) and its gradients on the run-time-shaped matrix-core
+# kernels (csrc/mnf_maf_rt.hip, mnf_maf_bwd_rt.hip; flows.MAF._rt): from this many rows on -- the smallest of
+# the measured row counts (2,048 / 8,192 / 65,536 / 262,144 at (dim, hidden) = (2, 24x3), (6, 16x2), (64, 24x3), (64, 64x2))
+# at which they are not slower than the VALU kernel on ALL three passes (forward, backward, forward + backward) for every
+# timed shape, and never below RT_MIN_ROWS (tools/time_maf_rt.py, profiles/r14/maf_rt_ab.txt).  They win every cell, the
+# narrowest one being (6, 16x2) forward + backward at 65,536 rows, 3.7 against 4.1 ns per row (at 2,048 rows: 90 against 129);
+# (64, 64x2) at 262,144 rows: 0.47 against 49 forward, 4.8 against 543 backward.  The fifth timed shape, (256, 64), has no VALU kernel to compare with (its masked
+# weights do not fit mnf_maf's 144 KB of LDS): from this many rows on it runs, below it is refused as before.  None would
+# mean opt-in: only a layer's force_generic = 2 reaches the kernels.
+MAF_RT_MIN_ROWS = 2048
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -163,12 +179,18 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
-    "nsf" | "rnvp" | "glow", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3; Glow: ();
-    Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's)."""
+    "nsf" | "rnvp" | "glow" | "maf", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
+    Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
+    MAF / IAF, hidden = MADE's hidden sizes -- the element-by-element direction is "valu" always)."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
+    if kind == "maf":
+        if MAF_RT_MIN_ROWS is None or rows < MAF_RT_MIN_ROWS or not wants_rt(rows):
+            return "valu"
+        query = lib.mnf_maf_rt_supported if direction == "fwd" else lib.mnf_maf_bwd_rt_supported
+        return "rt" if query(dim, n, hid) else "valu"
     if kind == "ahf":
         if direction == "fwd":
             per_shape = lib.mnf_affine_half_image_floats(dim, n, hid, int(scale), int(shift)) > 0

@@ -1,0 +1,218 @@
+// The one-pass direction of MAF / IAF (MAF.inverse, IAF.forward: torch_mnf/flows/maf.py:53-62) for ANY MADE shape on the
+// f16 matrix pipe: net = MADE(dim, h_1 .. h_n, 2 dim) (layers/made.py: MaskedLinear + ReLU) with any number of hidden
+// layers of widths 4 .. 128, any dim; run-time shapes (mnf_rt.h), weights read from the plain `flat` parameter vector,
+// masks from the byte buffer mnf_maf takes.  That direction is one pass of a masked MLP followed by z = x e^s + t --
+// nothing about it is sequential; the element-by-element direction stays on the VALU kernel of mnf_maf.hip.
+//
+// A wave owns one 16-row tile: the last hidden vector with the row streamed from memory K-step by K-step (every input
+// column: the masks do the autoregressive part), then the last MaskedLinear walked 16 output dims at a time as two heads,
+// s = rows 0 .. dim-1 and t = rows dim .. 2 dim-1: y_j = x_j e^{s_j} + t_j, stored at column dim-1-j when `parity`, and the
+// row's log|det J| = sum_j s_j in registers.  A masked-out weight is staged as exactly 0 (a select), and the scan for the
+// launch's staging exponent leaves it out.  One size class (8 hidden tiles), resident and streaming, the rows' alignment
+// taken at run time: the library's size budget holds no more.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "../../include/mnf_hip.h"
+#include "mnf_host.h"
+#include "mnf_rnvp_common.h"
+#include "mnf_rt.h"
+
+namespace mnf {
+
+struct MafRtArgs {
+  const float* x;
+  float* y;
+  float* log_det;
+  const float* flat;
+  const uint8_t* masks;
+  int64_t rows;
+  int dim, parity, accumulate;
+  int n_params, vec;  // vec: rows are 16-byte aligned and dim % 4 == 0 (dwordx4 row accesses)
+  int s_w, s_b;       // float offsets of the last MaskedLinear (s = its first dim rows, t = the next dim)
+  int cb, bt;
+  int block_words, bias_words;
+  int m_off[MNF_MAX_LINEAR];  // byte offset of layer l's mask
+  NetDesc net;                // dim -> h_1 .. h_n: the layers that end in a hidden vector
+};
+
+template <int MT_MAX, bool PREFILL, typename Src>
+__device__ __forceinline__ void maf_rt_block(const MafRtArgs& a, Src& src, float wup, int64_t row0) {
+  using namespace rt;
+  const bool VEC = a.vec != 0;  // (uniform)
+  constexpr int NTL = 1;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
+  const int d = a.dim;
+  const int64_t r = row0 + (int64_t)wave * 16 + j;
+  const bool live = !PREFILL && r < a.rows;
+  const int64_t rc = r < a.rows ? r : a.rows - 1;
+  const float* xrow = a.x + rc * d;
+  float* yrow = a.y + rc * d;
+
+  Hidden<MT_MAX, NTL> h;
+  auto load_x = [&](int, int ks, f32x4& xa, f32x4& xb) {
+    const int c0 = 32 * ks + 4 * q;
+    xa = load4(xrow, c0, d, VEC);
+    xb = load4(xrow, c0 + 16, d, VEC);
+  };
+  auto use_x = [&](int, int, const f32x4&, const f32x4&) {};
+  const int n_hid = a.net.n_lin;  // every layer of `net` ends in a hidden vector, each with its ReLU
+  const MaskedLayers layers{a.masks, a.m_off, a.net.sizes};
+  net_to_hidden<MT_MAX, NTL, PREFILL>(src, a.flat, a.net, n_hid, -1, wup, lane, q, load_x, use_x, h, NoLayerHook(), layers);
+
+  // ---- the last MaskedLinear, 16 output dims at a time: blocks [tile][s | t][K-step]
+  const int hl = a.net.sizes[n_hid];
+  const int KS = steps32(16 * tiles16(hl)), M = tiles16(d);
+  int MO = Src::resident ? M : src.cb / (2 * KS);
+  if (!Src::resident && MO > src.bt / 2) MO = src.bt / 2;
+  if (MO < 1) MO = 1;
+  const float* W0 = a.flat + a.s_w;
+  const float* B0 = a.flat + a.s_b;
+  const uint8_t* M0 = a.masks + a.m_off[n_hid];
+  float ld = 0.f;
+  f32x4 nx;  // the next tile's columns (requested one tile ahead)
+  if (!PREFILL) nx = load4(xrow, 4 * q, d, VEC);
+  for (int m0 = 0; m0 < M; m0 += MO) {
+    const int mo = M - m0 < MO ? M - m0 : MO;
+    const Chunk c = src.template chunk<PREFILL>(mo * 2 * KS, MaskedMMajor{W0, hl, d, KS, m0, 2, (int64_t)d * hl, M0, 2 * d, d},
+                                                mo * 2, DenseBiasHeads{B0, d, m0, 2, d});
+    if (PREFILL) continue;
+    for (int ml = 0; ml < mo; ++ml) {
+      const int m = m0 + ml, col = 16 * m + 4 * q;
+      const f32x4 xx = nx;
+      const int m_next = m + 1 < M ? m + 1 : M - 1;
+      nx = load4(xrow, 16 * m_next + 4 * q, d, VEC);
+      f32x4 s4[NTL], t4[NTL];
+      out_tile<MT_MAX, NTL>(c.A, (ml * 2) * KS, KS, c.bias + (ml * 2) * 16, lane, q, h, wup, s4);
+      out_tile<MT_MAX, NTL>(c.A, (ml * 2 + 1) * KS, KS, c.bias + (ml * 2 + 1) * 16, lane, q, h, wup, t4);
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        o[e] = __builtin_fmaf(xx[e], exp6r(s4[0][e]), t4[0][e]);  // (:57)
+        ld += col + e < d ? s4[0][e] : 0.f;                       // padding columns: s = 0
+      }
+      if (!a.parity) {  // (uniform)
+        store4(yrow, col, d, VEC, live, o);
+      } else if (VEC) {  // z.flip(dims=(1,)) (:58): columns col .. col + 3 land on d-1-col .. d-4-col, one dwordx4 (d % 4 == 0)
+        if (live && col < d) *reinterpret_cast<f32x4*>(yrow + (d - 4 - col)) = f32x4{o[3], o[2], o[1], o[0]};
+      } else if (live) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (col + e < d) yrow[d - 1 - col - e] = o[e];
+      }
+    }
+  }
+  if (PREFILL) return;
+  const float total = sum_over_q(ld);
+  if (q == 0 && live && a.log_det) a.log_det[r] = a.accumulate ? a.log_det[r] + total : total;
+}
+
+template <int MT_MAX, int NW, bool RESIDENT>
+__global__ void __launch_bounds__(NW * 64) maf_rt_kernel(MafRtArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t rt_lds[];
+  float* scratch = reinterpret_cast<float*>(rt_lds);
+  uint32_t* blocks = rt_lds + 16;
+  float* bias = reinterpret_cast<float*>(blocks + a.block_words);
+  const int n_hid = a.net.n_lin;
+  float wmx = rt::net_weight_max(a.flat, a.net, a.masks, a.m_off, 0.f);
+  wmx = rt::masked_abs_max(a.flat + a.s_w, a.masks + a.m_off[n_hid], a.net.sizes[n_hid], 2 * a.dim, wmx);
+  const float wmax = rt::block_weight_max(wmx, scratch);
+  const int e = rt::weight_exponent(wmax);
+  const float wup = rt::pow2f(e);
+  rt::Source<RESIDENT> src{blocks, bias, a.cb, a.bt, 0, 0, 0, rt::pow2f(-e), 0};
+  if (RESIDENT) {
+    maf_rt_block<MT_MAX, true>(a, src, wup, 0);
+    __syncthreads();
+  }
+  const int64_t rows_per_block = (int64_t)(blockDim.x >> 6) * 16;
+  const int64_t n_blocks = (a.rows + rows_per_block - 1) / rows_per_block;
+  for (int64_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+    src.slot = 0;
+    src.btile = 0;
+    maf_rt_block<MT_MAX, false>(a, src, wup, b * rows_per_block);
+  }
+}
+
+constexpr int kMafRtClass = 8, kMafRtWaves = 8;  // the one size class built: hidden widths up to 128
+
+// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.
+static bool maf_rt_plan(int dim, int n_hidden, const int* hidden, MafRtArgs& a, RtPlan& p) {
+  if (dim < 1 || n_hidden < 1 || !hidden_ok(n_hidden, hidden)) return false;
+  int sizes[MNF_MAX_LINEAR + 1];
+  sizes[0] = dim;
+  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
+  if (w.min < 4 || w.max > 16 * kMafRtClass) return false;
+  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0), moff = 0;
+  const int hl = hidden[n_hidden - 1];
+  for (int l = 0; l < n_hidden; ++l) {
+    a.m_off[l] = (int)moff;
+    moff += (int64_t)sizes[l] * sizes[l + 1];
+  }
+  a.m_off[n_hidden] = (int)moff;
+  moff += 2ll * dim * hl;
+  a.s_w = (int)off; off += 2ll * dim * hl;
+  a.s_b = (int)off; off += 2ll * dim;
+  if (off >= (1ll << 31) || moff >= (1ll << 31)) return false;
+  a.n_params = (int)off;
+  int64_t n_blocks = 0, n_bias = 0;
+  for (int l = 0; l < n_hidden; ++l) {
+    const int in_cols = l == 0 ? dim : 16 * ((sizes[l] + 15) / 16);
+    n_blocks += (int64_t)((in_cols + 31) / 32) * ((sizes[l + 1] + 15) / 16);
+    n_bias += (sizes[l + 1] + 15) / 16;
+  }
+  const int KS = (16 * ((hl + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
+  n_blocks += 2ll * KS * M;
+  n_bias += 2ll * M;
+  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
+  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
+  p.mt_max = kMafRtClass;
+  a.cb = p.resident ? (int)n_blocks : kStream;
+  a.bt = p.resident ? (int)n_bias : kStream;
+  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
+  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
+  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
+  p.nw = kMafRtWaves;
+  return true;
+}
+
+}  // namespace mnf
+
+using namespace mnf;
+
+extern "C" int mnf_maf_rt_supported(int dim, int n_hidden, const int* hidden) {
+  MafRtArgs a;
+  RtPlan p;
+  return maf_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+}
+
+static void (*maf_rt_kernel_of(const RtPlan& p))(MafRtArgs) {
+  static DeviceMemo attr;
+  allow_big_lds(attr, maf_rt_kernel<kMafRtClass, kMafRtWaves, true>, maf_rt_kernel<kMafRtClass, kMafRtWaves, false>);
+  return p.resident ? maf_rt_kernel<kMafRtClass, kMafRtWaves, true> : maf_rt_kernel<kMafRtClass, kMafRtWaves, false>;
+}
+
+// workgroups of the launch (each walks the row blocks of 16 x 8 rows blockIdx.x, + grid, ...); 0: no launch, or no device
+extern "C" int64_t mnf_maf_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden) {
+  MafRtArgs a;
+  RtPlan p;
+  if (rows < 1 || !maf_rt_plan(dim, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
+  return persistent_grid(maf_rt_kernel_of(p), p.nw, p.lds, (int64_t)p.nw * 16, rows);
+}
+
+extern "C" int mnf_maf_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
+                          int64_t rows, int dim, int parity, int n_hidden, const int* hidden, void* stream) {
+  if (!x || !y || x == y || !flat || !masks || rows < 0 || dim < 1 || n_hidden < 1 || !hidden_ok(n_hidden, hidden))
+    return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  if (rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
+  MafRtArgs a;
+  memset(&a, 0, sizeof(a));
+  RtPlan p;
+  if (!maf_rt_plan(dim, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
+  a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.masks = masks; a.rows = rows; a.dim = dim;
+  a.parity = parity != 0;
+  a.accumulate = accumulate != 0;
+  a.vec = dim % 4 == 0 && aligned16(x, y);
+  return launch_persistent(maf_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "maf_rt", (hipStream_t)stream);
+}

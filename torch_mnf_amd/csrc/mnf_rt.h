@@ -77,6 +77,25 @@ __device__ __forceinline__ float net_weight_max(const float* __restrict__ flat, 
   return mx;
 }
 
+// the same over MADE's MaskedLinear layers (mnf_maf: byte masks of shape (n_in_l, n_out_l) per layer, back to back, layer l
+// at masks + m_off[l]; the byte of W[o][k] is mask[k * n_out + o]): a masked-out weight is never multiplied, so it must not
+// set the launch's staging exponent either
+__device__ __forceinline__ float masked_abs_max(const float* __restrict__ w, const uint8_t* __restrict__ mask, int n_in, int n_out,
+                                                float mx) {
+  for (int i = threadIdx.x; i < n_in * n_out; i += blockDim.x) {
+    const int o = i / n_in, k = i - o * n_in;
+    const float a = finite_abs(w[i]);
+    mx = __builtin_fmaxf(mx, mask[(int64_t)k * n_out + o] ? a : 0.f);
+  }
+  return mx;
+}
+__device__ __forceinline__ float net_weight_max(const float* __restrict__ flat, const NetDesc& nd, const uint8_t* __restrict__ masks,
+                                                const int* m_off, float mx) {
+  for (int l = 0; l < nd.n_lin; ++l)
+    mx = masked_abs_max(flat + nd.w_off[l], masks + m_off[l], nd.sizes[l], nd.sizes[l + 1], mx);
+  return mx;
+}
+
 // mx: the thread's share (range_abs_max / net_weight_max over every weight range of the layer).  scratch: >= 16 floats of
 // LDS; ends with a barrier; every thread returns the same value
 __device__ __forceinline__ float block_weight_max(float mx, float* scratch) {
@@ -233,6 +252,48 @@ struct DenseBiasHeads {  // tile t = (m - m0) * heads + head
   }
 };
 
+// The same two walks over a MaskedLinear (made.py:22-23: x @ (W.T * mask) + b; the mask is (n_in, n_out) bytes, the byte of
+// W[o][k] at M[k * ldm + o], ldm = the layer's n_out): a weight whose byte is 0 is staged as exactly 0 -- by a select, never
+// by a multiply, so that an inf or NaN left in a masked-out slot stays out.  The byte is read at a clamped index like the
+// weight itself: no load under a divergent branch.
+__device__ __forceinline__ void mask_row8(const uint8_t* __restrict__ M, int ldm, int o, bool row_ok, int c0, int n_cols, int q,
+                                          f32x4& va, f32x4& vb) {
+  const int ca = c0 + 4 * q, cb = ca + 16;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const bool oka = row_ok && ca + e < n_cols, okb = row_ok && cb + e < n_cols;
+    const uint8_t ma = M[oka ? (int64_t)(ca + e) * ldm + o : 0], mb = M[okb ? (int64_t)(cb + e) * ldm + o : 0];
+    va[e] = oka && ma ? va[e] : 0.f;
+    vb[e] = okb && mb ? vb[e] : 0.f;
+  }
+}
+struct MaskedKMajor {
+  const float* W;
+  int n_in, n_out, R0, ks0;  // R0 = MT
+  const uint8_t* M;
+  int ldm;
+  static constexpr int R1 = 1 << 30;
+  __device__ __forceinline__ void load(int m, int ksl, int, int i, int q, f32x4& va, f32x4& vb) const {
+    DenseKMajor{W, n_in, n_out, R0, ks0}.load(m, ksl, 0, i, q, va, vb);
+    const int o = 16 * m + i;
+    mask_row8(M, ldm, o, o < n_out, 32 * (ks0 + ksl), n_in, q, va, vb);
+  }
+};
+// head h: rows h * n_out .. of one MaskedLinear whose mask has ldm >= heads * n_out columns (mask column of row o of head h:
+// h * mask_head_stride + o)
+struct MaskedMMajor {
+  const float* W;
+  int n_in, n_out, R0, m0, R1;  // R0 = KS, R1 = heads
+  int64_t head_stride;
+  const uint8_t* M;
+  int ldm, mask_head_stride;
+  __device__ __forceinline__ void load(int ks, int head, int ml, int i, int q, f32x4& va, f32x4& vb) const {
+    DenseMMajor{W, n_in, n_out, R0, m0, R1, head_stride}.load(ks, head, ml, i, q, va, vb);
+    const int o = 16 * (m0 + ml) + i;
+    mask_row8(M + head * mask_head_stride, ldm, o, o < n_out, 32 * ks, n_in, q, va, vb);
+  }
+};
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Where a kernel's A blocks come from: resident (staged once, absolute slots) or streamed (two buffers, one barrier per
 // chunk).  chunk() is called by every wave of the workgroup at the same points.
@@ -352,15 +413,23 @@ __device__ __forceinline__ void split_kstep(const f32x4& a, const f32x4& b, floa
   bl = pair_operand(al, bl2);
 }
 
-// Accumulators -> activations -> the next layer's split tiles.  pre = (main + corr 2^-11) * scale + bias; LeakyReLU when
-// `act`.  scale[t] = wup * (the input rows' factor); tiles >= MT come out as zeros.
-template <int MT_MAX, int NTL>
+// Accumulators -> activations -> the next layer's split tiles.  pre = (main + corr 2^-11) * scale + bias; the activation
+// when `act`: LeakyReLU, or -- RELU -- ReLU, slope 0 (MADE, made.py: p < 0 ? 0 : p, i.e. max(p, 0) with a NaN kept as
+// torch.relu keeps it).  scale[t] = wup * (the input rows' factor); tiles >= MT come out as zeros.
+template <int MT_MAX, int NTL, bool RELU = false>
 __device__ __forceinline__ void finish_layer(const Acc<MT_MAX, NTL>& acc, const float* bias_tiles, int MT, int q,
                                              const float (&scale)[NTL], bool act, Hidden<MT_MAX, NTL>& h) {
   const f32x4 zero4 = f32x4{0.f, 0.f, 0.f, 0.f};
   auto value = [&](int t, int m, const f32x4& bias) {
     const f32x4 p = (acc.corr[t][m] * kSplitInvScale + acc.main[t][m]) * scale[t] + bias;
-    return act ? __builtin_elementwise_max(p, p * kLeakySlope) : p;
+    if constexpr (RELU) {
+      f32x4 v;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = act && p[r] < 0.f ? 0.f : p[r];
+      return v;
+    } else {
+      return act ? __builtin_elementwise_max(p, p * kLeakySlope) : p;
+    }
   };
   float mx = 0.f;
 #pragma unroll
@@ -459,13 +528,57 @@ struct DenseBiasN {
   }
 };
 
+template <int NN>
+struct MaskedKMajorN : DenseKMajorN<NN> {  // every net under the same mask (MAF has one net)
+  const uint8_t* M;
+  int ldm;
+  __device__ __forceinline__ void load(int mm, int ksl, int, int i, int q, f32x4& va, f32x4& vb) const {
+    DenseKMajorN<NN>::load(mm, ksl, 0, i, q, va, vb);
+    const int net = mm >= this->MT ? 1 : 0, o = 16 * (mm - net * this->MT) + i;
+    mask_row8(M, ldm, o, o < this->n_out, 32 * (this->ks0 + ksl), this->n_in, q, va, vb);
+  }
+};
+
+// What the Linear layers of a conditioner net are: plain Linear + LeakyReLU, or -- with a MaskedLayers as the OPTIONAL last
+// argument of the net walkers below and of mnf_rt_bwd.h's (a parameter pack of at most one) -- MADE's MaskedLinear + ReLU,
+// layer l's mask at masks + m_off[l] (MaskedLayersBwd, mnf_rt_bwd.h, adds the transposed walks and the weight-gradient
+// predicate).  Without the argument a walker has the parameters and the statements it had before MaskedLayers existed:
+// the kernels of plain Linear layers compile to the same device code (profiles/r14/README.md).
+template <typename T>
+__device__ __forceinline__ const T& only(const T& t) {
+  return t;
+}
+template <int NN, bool MASKED>
+struct FirstFetch {
+  typedef DenseKMajorN<NN> type;
+};
+template <int NN>
+struct FirstFetch<NN, true> {
+  typedef MaskedKMajorN<NN> type;
+};
+struct MaskedLayers {
+  const uint8_t* masks;
+  const int* m_off;
+  const int* sizes;  // the net's NetDesc::sizes (ldm of layer l = sizes[l + 1])
+  template <int NN>
+  __device__ __forceinline__ void bind_first(MaskedKMajorN<NN>& f) const {
+    f.M = masks + m_off[0];
+    f.ldm = sizes[1];
+  }
+  __device__ __forceinline__ MaskedKMajor kmajor(int l, const float* W, int n_in, int n_out, int R0, int ks0) const {
+    return MaskedKMajor{W, n_in, n_out, R0, ks0, masks + m_off[l], n_out};
+  }
+};
+
 // Layer 0 of NN nets of one shape over the same input, K-streamed: the input is loaded and split ONCE per K-step and
 // multiplied into every net's accumulators (NN = 2: AffineHalfFlow's s- and t-net at hidden widths <= 64 -- the input
 // side of a wide layer is most of its forward pass).  h[n] = H_1 of net n.
-template <int MT_MAX, int NTL, bool PREFILL, int NN, typename Src, typename LoadX, typename UseX, typename Hook = NoLayerHook>
+template <int MT_MAX, int NTL, bool PREFILL, int NN, typename Src, typename LoadX, typename UseX, typename Hook = NoLayerHook,
+          typename... Net>
 __device__ __forceinline__ void first_layer(Src& src, const float* __restrict__ flat, const NetDesc* const (&nds)[NN], bool act,
                                             float wup, int lane, int q, const LoadX& load_x, const UseX& use_x,
-                                            Hidden<MT_MAX, NTL> (&h)[NN], const Hook& hook = Hook()) {
+                                            Hidden<MT_MAX, NTL> (&h)[NN], const Hook& hook = Hook(), const Net&... net) {
+  constexpr bool kMasked = sizeof...(Net) != 0;
   Acc<MT_MAX, NTL> acc[NN];
   const NetDesc& nd = *nds[0];
   const int n_in = nd.sizes[0], n_out = nd.sizes[1];
@@ -489,7 +602,8 @@ __device__ __forceinline__ void first_layer(Src& src, const float* __restrict__ 
 #pragma unroll
       for (int t = 0; t < NTL; ++t) load_x(t, u < KS ? u : KS - 1, ra[u][t], rb[u][t]);
   }
-  DenseKMajorN<NN> fetch;
+  typename FirstFetch<NN, kMasked>::type fetch;
+  if constexpr (kMasked) only(net...).bind_first(fetch);
   DenseBiasN<NN> bias_fn;
 #pragma unroll
   for (int n = 0; n < NN; ++n) {
@@ -562,17 +676,18 @@ __device__ __forceinline__ void first_layer(Src& src, const float* __restrict__ 
     for (int t = 0; t < NTL; ++t) scale[t] = wup / down[t];
 #pragma unroll
     for (int n = 0; n < NN; ++n) {
-      finish_layer<MT_MAX, NTL>(acc[n], c.bias + 16 * n * MT, MT, q, scale, act, h[n]);
+      finish_layer<MT_MAX, NTL, kMasked>(acc[n], c.bias + 16 * n * MT, MT, q, scale, act, h[n]);
       if (n == 0) hook(1, h[0]);
     }
   }
 }
 
 // The hidden -> hidden layers 1 .. n_hid - 1 of one net in registers, from h = H_1 to h = H_{n_hid}.
-template <int MT_MAX, int NTL, bool PREFILL, typename Src, typename Hook = NoLayerHook>
+template <int MT_MAX, int NTL, bool PREFILL, typename Src, typename Hook = NoLayerHook, typename... Net>
 __device__ __forceinline__ void hidden_layers(Src& src, const float* __restrict__ flat, const NetDesc& nd, int n_hid,
                                               int no_act_layer, float wup, int lane, int q, Hidden<MT_MAX, NTL>& h,
-                                              const Hook& hook = Hook()) {
+                                              const Hook& hook = Hook(), const Net&... net) {
+  constexpr bool kMasked = sizeof...(Net) != 0;
   constexpr int KS_MAX = MT_MAX / 2;
   Acc<MT_MAX, NTL> acc;
   for (int l = 1; l < n_hid; ++l) {
@@ -589,8 +704,12 @@ __device__ __forceinline__ void hidden_layers(Src& src, const float* __restrict_
       if (ks < KS) {
         if (ks == next_start) {  // (uniform) a new chunk starts at this K-step
           const int kc = KS - ks < KC ? KS - ks : KC;
-          c = src.template chunk<PREFILL>(kc * MT, DenseKMajor{flat + nd.w_off[l], n_in, n_out, MT, ks}, ks + kc == KS ? MT : 0,
-                                 DenseBias{flat + nd.b_off[l], n_out, 0});
+          if constexpr (kMasked)
+            c = src.template chunk<PREFILL>(kc * MT, only(net...).kmajor(l, flat + nd.w_off[l], n_in, n_out, MT, ks), ks + kc == KS ? MT : 0,
+                                            DenseBias{flat + nd.b_off[l], n_out, 0});
+          else
+            c = src.template chunk<PREFILL>(kc * MT, DenseKMajor{flat + nd.w_off[l], n_in, n_out, MT, ks}, ks + kc == KS ? MT : 0,
+                                   DenseBias{flat + nd.b_off[l], n_out, 0});
           chunk_start = ks;
           next_start = ks + kc;
         }
@@ -604,21 +723,23 @@ __device__ __forceinline__ void hidden_layers(Src& src, const float* __restrict_
       float scale[NTL];
 #pragma unroll
       for (int t = 0; t < NTL; ++t) scale[t] = wup * h.up[t];
-      finish_layer<MT_MAX, NTL>(acc, c.bias, MT, q, scale, l != no_act_layer, h);
+      finish_layer<MT_MAX, NTL, kMasked>(acc, c.bias, MT, q, scale, l != no_act_layer, h);
       hook(l + 1, h);
     }
   }
 }
 
-template <int MT_MAX, int NTL, bool PREFILL, typename Src, typename LoadX, typename UseX, typename Hook = NoLayerHook>
+template <int MT_MAX, int NTL, bool PREFILL, typename Src, typename LoadX, typename UseX, typename Hook = NoLayerHook,
+          typename... Net>
 __device__ __forceinline__ void net_to_hidden(Src& src, const float* __restrict__ flat, const NetDesc& nd, int n_hid,
                                               int no_act_layer, float wup, int lane, int q, const LoadX& load_x,
-                                              const UseX& use_x, Hidden<MT_MAX, NTL>& h, const Hook& hook = Hook()) {
+                                              const UseX& use_x, Hidden<MT_MAX, NTL>& h, const Hook& hook = Hook(),
+                                              const Net&... net) {
   const NetDesc* const nds[1] = {&nd};
   Hidden<MT_MAX, NTL> h1[1];
-  first_layer<MT_MAX, NTL, PREFILL, 1>(src, flat, nds, no_act_layer != 0, wup, lane, q, load_x, use_x, h1, hook);
+  first_layer<MT_MAX, NTL, PREFILL, 1>(src, flat, nds, no_act_layer != 0, wup, lane, q, load_x, use_x, h1, hook, net...);
   h = h1[0];
-  hidden_layers<MT_MAX, NTL, PREFILL>(src, flat, nd, n_hid, no_act_layer, wup, lane, q, h, hook);
+  hidden_layers<MT_MAX, NTL, PREFILL>(src, flat, nd, n_hid, no_act_layer, wup, lane, q, h, hook, net...);
 }
 
 // One output tile from a last-hidden vector: the KS blocks at A + b0, bias tile `bias16` (16 floats), scale as in

@@ -99,11 +99,23 @@ struct ContigRows {
     return o < n_out ? o : -1;
   }
 };
-template <typename RowMap>
+// An optional last argument keep(o, k, in) of dw_phase_rows / dw_phase (a pack of at most one): does dW[o][k] receive this
+// add?  `in` = the entry exists (o >= 0, k < n_in).  Without it: every entry that exists.  MaskKeep: a MaskedLinear's live
+// weights only -- a masked-out one gets exactly no add, neither atomic nor into a slot (the byte is read at a clamped
+// index: no load under a divergent branch).  Biases have no mask.
+struct MaskKeep {
+  const uint8_t* M;  // the byte of W[o][k] at M[k * ldm + o]
+  int ldm;
+  __device__ __forceinline__ bool operator()(int o, int k, bool in) const {
+    const uint8_t b = M[in ? (int64_t)k * ldm + o : 0];
+    return in && b != 0;
+  }
+};
+template <typename RowMap, typename... Keep>
 __device__ __forceinline__ void dw_phase_rows(const Exchange& exa, int a0, int MA, const Exchange& exb, int b0, int MB,
                                               const float* sa, const float* sb, int nw, float out_scale,
                                               float* __restrict__ gW, float* __restrict__ gb, const RowMap& rows, int n_in,
-                                              int n0) {
+                                              int n0, const Keep&... keep) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
   const int us = exa.unit_stride();
   f16x4 ones;
@@ -156,16 +168,21 @@ __device__ __forceinline__ void dw_phase_rows(const Exchange& exa, int a0, int M
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int o = rows(m, 4 * q + r);
-      if (o >= 0 && k < n_in) atomicAdd(gW + (size_t)o * n_in + k, acc[r] * out_scale);
+      if constexpr (sizeof...(Keep) != 0) {
+        if (only(keep...)(o, k, o >= 0 && k < n_in)) atomicAdd(gW + (size_t)o * n_in + k, acc[r] * out_scale);
+      } else {
+        if (o >= 0 && k < n_in) atomicAdd(gW + (size_t)o * n_in + k, acc[r] * out_scale);
+      }
       if (gb && n == 0 && i == 0 && o >= 0) atomicAdd(gb + o, bacc[r] * out_scale);
     }
     n += nw;
   }
 }
+template <typename... Keep>
 __device__ __forceinline__ void dw_phase(const Exchange& exa, int a0, int MA, const Exchange& exb, int b0, int MB,
                                          const float* sa, const float* sb, int nw, float out_scale, float* __restrict__ gW,
-                                         float* __restrict__ gb, int n_out, int n_in, int m0, int n0) {
-  dw_phase_rows(exa, a0, MA, exb, b0, MB, sa, sb, nw, out_scale, gW, gb, ContigRows{m0, n_out}, n_in, n0);
+                                         float* __restrict__ gb, int n_out, int n_in, int m0, int n0, const Keep&... keep) {
+  dw_phase_rows(exa, a0, MA, exb, b0, MB, sa, sb, nw, out_scale, gW, gb, ContigRows{m0, n_out}, n_in, n0, keep...);
 }
 
 // W^T of a dense Linear W (n_out x n_in) as A blocks: block row i = INPUT unit 16 mi + i, K index = OUTPUT unit.
@@ -195,6 +212,46 @@ struct DenseTMMajor {
     DenseTKMajor{W, n_in, n_out, 1, ks}.load(m0 + ml, 0, 0, i, q, va, vb);
   }
 };
+// the two transposed walks over a MaskedLinear (mnf_rt.h MaskedKMajor: the byte of W[o][k] at M[k * ldm + o])
+struct MaskedTKMajor {
+  const float* W;
+  int n_in, n_out, R0, ks0;  // R0 = input tiles
+  const uint8_t* M;
+  int ldm;
+  static constexpr int R1 = 1 << 30;
+  __device__ __forceinline__ void load(int mi, int ksl, int, int i, int q, f32x4& va, f32x4& vb) const {
+    DenseTKMajor{W, n_in, n_out, R0, ks0}.load(mi, ksl, 0, i, q, va, vb);
+    const int u = 16 * mi + i, o0 = 32 * (ks0 + ksl) + 4 * q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int oa = o0 + e, ob = oa + 16;
+      const bool oka = u < n_in && oa < n_out, okb = u < n_in && ob < n_out;
+      const uint8_t ma = M[oka ? (int64_t)u * ldm + oa : 0], mb = M[okb ? (int64_t)u * ldm + ob : 0];
+      va[e] = oka && ma ? va[e] : 0.f;
+      vb[e] = okb && mb ? vb[e] : 0.f;
+    }
+  }
+};
+struct MaskedTMMajor {
+  const float* W;
+  int n_in, n_out, R0, m0;  // R0 = KS over the outputs
+  const uint8_t* M;
+  int ldm;
+  static constexpr int R1 = 1 << 30;
+  __device__ __forceinline__ void load(int ks, int ml, int, int i, int q, f32x4& va, f32x4& vb) const {
+    MaskedTKMajor{W, n_in, n_out, 1, ks, M, ldm}.load(m0 + ml, 0, 0, i, q, va, vb);
+  }
+};
+// mnf_rt.h's MaskedLayers with what the gradient direction adds: the transposed walks and dw_phase's predicate.
+struct MaskedLayersBwd : MaskedLayers {
+  __device__ __forceinline__ MaskedTKMajor tkmajor(int l, const float* W, int n_in, int n_out, int R0, int ks0) const {
+    return MaskedTKMajor{W, n_in, n_out, R0, ks0, masks + m_off[l], n_out};
+  }
+  __device__ __forceinline__ MaskedTMMajor tmmajor(int l, const float* W, int n_in, int n_out, int R0, int m0) const {
+    return MaskedTMMajor{W, n_in, n_out, R0, m0, masks + m_off[l], n_out};
+  }
+  __device__ __forceinline__ MaskKeep keep(int l, int n_out) const { return MaskKeep{masks + m_off[l], n_out}; }
+};
 struct NoBias {
   __device__ __forceinline__ float operator()(int, int) const { return 0.f; }
 };
@@ -208,15 +265,16 @@ __device__ __forceinline__ bool split_positive(uint32_t hi_word, uint32_t lo_wor
   return half != 0u && (half & 0x8000u) == 0u;
 }
 
-// the LeakyReLU derivative of a hidden vector from its (split) values: sign of the head part, per unit
-template <int MT_MAX>
+// the LeakyReLU (RELU: the ReLU, slope 0 -- and 0 at 0, split_positive answers false for a zero) derivative of a hidden
+// vector from its (split) values: sign of the head part, per unit
+template <int MT_MAX, bool RELU = false>
 __device__ __forceinline__ void leaky_gate(const Hidden<MT_MAX, 1>& h, f32x4 (&g)[MT_MAX]) {
 #pragma unroll
   for (int m = 0; m < MT_MAX; ++m) {
     // packed f16 pairs: element r of the tile sits in half (r & 1) of word (r >> 1); positive <=> sign bit clear and non-zero
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      g[m][r] = split_positive(h.hi[0][m][r >> 1], h.lo[0][m][r >> 1], r & 1) ? 1.f : kLeakySlope;
+      g[m][r] = split_positive(h.hi[0][m][r >> 1], h.lo[0][m][r >> 1], r & 1) ? 1.f : RELU ? 0.f : kLeakySlope;
     }
   }
 }
@@ -236,14 +294,17 @@ __device__ __forceinline__ uint32_t pack_signs(const Hidden<MT_MAX, 1>& h) {
   return bits;
 }
 
-// (main + corr 2^-11) * scale, times the LeakyReLU derivative of the hidden vector whose sign bits are `bits`
-template <int MT_MAX>
+// (main + corr 2^-11) * scale, times the LeakyReLU (RELU: ReLU) derivative of the hidden vector whose sign bits are `bits`
+template <int MT_MAX, bool RELU = false>
 __device__ __forceinline__ void chain_result(const Acc<MT_MAX, 1>& acc, float scale, uint32_t bits, f32x4 (&dv)[MT_MAX]) {
 #pragma unroll
   for (int m = 0; m < MT_MAX; ++m) {
     const f32x4 p = (acc.corr[0][m] * kSplitInvScale + acc.main[0][m]) * scale;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) dv[m][r] = p[r] * ((bits >> (4 * m + r)) & 1u ? 1.f : kLeakySlope);
+    for (int r = 0; r < 4; ++r) {
+      if constexpr (RELU) dv[m][r] = (bits >> (4 * m + r)) & 1u ? p[r] : 0.f;
+      else dv[m][r] = p[r] * ((bits >> (4 * m + r)) & 1u ? 1.f : kLeakySlope);
+    }
   }
 }
 
@@ -322,10 +383,10 @@ inline size_t bwd_lds_bytes(int nw, int ht_tiles, int dt_tiles, int ct_tiles) {
 
 // The forward recompute of one conditioner net that KEEPS every hidden vector: its true values turned into the exchange
 // area (tiles from exH tile 0 on, with the wave-tile's scale in sH[i][wave]) and its sign bits (the LeakyReLU derivative).
-template <int MT_MAX, typename Src, typename LoadX>
+template <int MT_MAX, typename Src, typename LoadX, typename... Net>
 __device__ __forceinline__ void forward_keep(Src& src, const float* __restrict__ flat, const NetDesc& nd, int n_hid,
                                              int no_act_layer, float wup, const BwdLds& L, const LoadX& load_x,
-                                             Hidden<MT_MAX, 1>& h) {
+                                             Hidden<MT_MAX, 1>& h, const Net&... net) {
   auto use_x = [&](int, int, const f32x4&, const f32x4&) {};
   int tile0 = 0;
   auto hook = [&](int i, const Hidden<MT_MAX, 1>& hh) {
@@ -337,7 +398,7 @@ __device__ __forceinline__ void forward_keep(Src& src, const float* __restrict__
     tile0 += MT;
     L.meta_bits[i * 64 + L.lane] = pack_signs<MT_MAX>(hh);
   };
-  net_to_hidden<MT_MAX, 1, false>(src, flat, nd, n_hid, no_act_layer, wup, L.lane, L.q, load_x, use_x, h, hook);
+  net_to_hidden<MT_MAX, 1, false>(src, flat, nd, n_hid, no_act_layer, wup, L.lane, L.q, load_x, use_x, h, hook, net...);
 }
 
 // From dv = the cotangent of H_n's pre-activation (n = n_hid; in units of the gradient scale) down to the net's input:
@@ -345,10 +406,12 @@ __device__ __forceinline__ void forward_keep(Src& src, const float* __restrict__
 // act'(H_{i-1});  then the first layer input tile by input tile: add_in(mi, W_0^T delta_1 of the tile's 16 columns, times
 // inv_gs) and dW_0 += delta_1 (x) load_in(mi).  n_in0 = the first layer's input width.  The hidden vector whose index is
 // no_act_hidden has no activation (derivative 1).
-template <int MT_MAX, typename Src, typename LoadIn, typename AddIn>
+template <int MT_MAX, typename Src, typename LoadIn, typename AddIn, typename... Net>
 __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict__ flat, float* gflat, const NetDesc& nd,
                                               int n_hid, int no_act_hidden, f32x4 (&dv)[MT_MAX], const BwdLds& L, float wup,
-                                              float inv_gs, int n_in0, const LoadIn& load_in, const AddIn& add_in) {
+                                              float inv_gs, int n_in0, const LoadIn& load_in, const AddIn& add_in,
+                                              const Net&... net) {
+  constexpr bool kMasked = sizeof...(Net) != 0;
   const int lane = L.lane, wave = L.wave, q = L.q, nw = L.nw;
 #pragma unroll 1
   for (int i = n_hid; i >= 2; --i) {
@@ -362,8 +425,12 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
       const float sc = exchange_store<MT_MAX>(dv, MTi, exD, 0, 16 * wave, lane, L.ident);
       if (lane == 0) L.sA[wave] = sc;
       lds_barrier();
-      dw_phase(exD, 0, MTi, L.exH, exH_tile_of(nd, i - 1), MTp, L.sA, L.sH + (i - 1) * 8, nw, inv_gs, gflat + nd.w_off[i - 1],
-               gflat + nd.b_off[i - 1], nd.sizes[i], nd.sizes[i - 1], 0, 0);
+      if constexpr (kMasked)
+        dw_phase(exD, 0, MTi, L.exH, exH_tile_of(nd, i - 1), MTp, L.sA, L.sH + (i - 1) * 8, nw, inv_gs, gflat + nd.w_off[i - 1],
+                 gflat + nd.b_off[i - 1], nd.sizes[i], nd.sizes[i - 1], 0, 0, only(net...).keep(i - 1, nd.sizes[i]));
+      else
+        dw_phase(exD, 0, MTi, L.exH, exH_tile_of(nd, i - 1), MTp, L.sA, L.sH + (i - 1) * 8, nw, inv_gs, gflat + nd.w_off[i - 1],
+                 gflat + nd.b_off[i - 1], nd.sizes[i], nd.sizes[i - 1], 0, 0);
     }
     // delta_{i-1} = (W_{i-1}^T delta_i) * act'(H_{i-1}): K = the units of H_i, output tiles = those of H_{i-1}
     Hidden<MT_MAX, 1> hd;
@@ -381,7 +448,10 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
         if (ks == next_start) {
           const int kc = KS - ks < KC ? KS - ks : KC;
           uint32_t* b = src.cur_blocks();
-          stage_blocks(b, kc * MTp, DenseTKMajor{flat + nd.w_off[i - 1], nd.sizes[i - 1], nd.sizes[i], MTp, ks}, src.wdown);
+          if constexpr (kMasked)
+            stage_blocks(b, kc * MTp, only(net...).tkmajor(i - 1, flat + nd.w_off[i - 1], nd.sizes[i - 1], nd.sizes[i], MTp, ks), src.wdown);
+          else
+            stage_blocks(b, kc * MTp, DenseTKMajor{flat + nd.w_off[i - 1], nd.sizes[i - 1], nd.sizes[i], MTp, ks}, src.wdown);
           src.commit();
           bufT = b;
           chunk_start = ks;
@@ -391,7 +461,7 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
         hidden_operand<MT_MAX, 1>(hd, ks, bh, bl);
         mac_kstep<MT_MAX, 1>(bufT, (ks - chunk_start) * MTp, MTp, lane, bh, bl, acc.main, acc.corr);
       }
-    chain_result<MT_MAX>(acc, wup * hd.up[0], i - 1 == no_act_hidden ? 0xffffffffu : L.meta_bits[(i - 1) * 64 + lane], dv);
+    chain_result<MT_MAX, kMasked>(acc, wup * hd.up[0], i - 1 == no_act_hidden ? 0xffffffffu : L.meta_bits[(i - 1) * 64 + lane], dv);
   }
   // ---- first layer: dv = delta_1
   const int MT1 = tiles16(nd.sizes[1]), KS1 = steps32(16 * MT1), MI = tiles16(n_in0);
@@ -411,7 +481,10 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
     const int ci = MI - mi0 < CI ? MI - mi0 : CI;
     uint32_t* buf = src.cur_blocks();
     float* bbuf = src.cur_bias();
-    stage_blocks(buf, ci * KS1, DenseTMMajor{flat + nd.w_off[0], n_in0, nd.sizes[1], KS1, mi0}, src.wdown);
+    if constexpr (kMasked)
+      stage_blocks(buf, ci * KS1, only(net...).tmmajor(0, flat + nd.w_off[0], n_in0, nd.sizes[1], KS1, mi0), src.wdown);
+    else
+      stage_blocks(buf, ci * KS1, DenseTMMajor{flat + nd.w_off[0], n_in0, nd.sizes[1], KS1, mi0}, src.wdown);
     stage_bias(bbuf, 1, NoBias{});
     src.commit();
     f32x4 xv[MT_MAX];
@@ -429,8 +502,12 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
       const float sc = exchange_store<MT_MAX>(xv, ci, L.exC, 0, 16 * wave, lane, L.ident);
       if (lane == 0) L.sC[wave] = sc;
       lds_barrier();
-      dw_phase(exD1, 0, MT1, L.exC, 0, ci, L.sA, L.sC, nw, inv_gs, gflat + nd.w_off[0], mi0 == 0 ? gflat + nd.b_off[0] : nullptr,
-               nd.sizes[1], n_in0, 0, mi0);
+      if constexpr (kMasked)
+        dw_phase(exD1, 0, MT1, L.exC, 0, ci, L.sA, L.sC, nw, inv_gs, gflat + nd.w_off[0], mi0 == 0 ? gflat + nd.b_off[0] : nullptr,
+                 nd.sizes[1], n_in0, 0, mi0, only(net...).keep(0, nd.sizes[1]));
+      else
+        dw_phase(exD1, 0, MT1, L.exC, 0, ci, L.sA, L.sC, nw, inv_gs, gflat + nd.w_off[0], mi0 == 0 ? gflat + nd.b_off[0] : nullptr,
+                 nd.sizes[1], n_in0, 0, mi0);
     }
   }
 }

@@ -1748,7 +1748,8 @@ class RNVP(_HipFlow):
 
 
 class _MafFn(torch.autograd.Function):
-    """MAF / IAF with gradients (mnf_maf / mnf_maf_bwd).  ``home``: see _RnvpFn."""
+    """MAF / IAF with gradients (mnf_maf / mnf_maf_bwd; the one-pass direction on mnf_maf_rt / mnf_maf_bwd_rt where
+    MAF._rt says so).  ``home``: see _RnvpFn."""
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, sequential, home=None):
@@ -1756,9 +1757,7 @@ class _MafFn(torch.autograd.Function):
         masks = module._mask_bytes(x.device)
         y = torch.empty_like(x)
         ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_maf", _lib.load().mnf_maf(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), 0, flat.data_ptr(), masks.data_ptr(), x.shape[0], module.dim,
-            int(bool(module.parity)), int(sequential), len(module.h_sizes), module._hid, _stream()))
+        module._launch(x, y, ld, 0, flat, masks, sequential)
         ctx.module, ctx.sequential, ctx.home = module, sequential, home
         ctx.save_for_backward(x, y, flat, masks)
         return y, ld
@@ -1774,9 +1773,26 @@ class _MafFn(torch.autograd.Function):
             grad_flat, ret = home[0].grad[home[1]:home[1] + home[2]], None
         else:
             grad_flat = ret = torch.zeros_like(flat)
-        _lib.check("mnf_maf_bwd", _lib.load().mnf_maf_bwd(
+        lib, rows = _lib.load(), x.shape[0]
+        if m._rt(rows, ctx.sequential, bwd=True):
+            # the one-pass direction on the run-time-shaped matrix-core kernel (1..4 hidden layers of widths 4..64)
+            scale = _grad_scale(gy, gl, rows, m.dim, x.device)
+            rt_args = (x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
+                       masks.data_ptr(), scale.data_ptr(), rows, m.dim, int(bool(m.parity)), len(m.h_sizes), m._hid)
+            rc = _lib.MNF_ERR_UNSUPPORTED
+            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
+                n_ws = lib.mnf_maf_bwd_rt_det_workspace(rows, m.dim, len(m.h_sizes), m._hid)
+                if n_ws > 0:
+                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
+                    rc = lib.mnf_maf_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
+            else:
+                rc = lib.mnf_maf_bwd_rt(*rt_args, _stream())
+            if rc != _lib.MNF_ERR_UNSUPPORTED:
+                _lib.check("mnf_maf_bwd_rt", rc)
+                return grad_x, ret, None, None, None
+        _lib.check("mnf_maf_bwd", lib.mnf_maf_bwd(
             x.data_ptr(), y.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
-            masks.data_ptr(), x.shape[0], m.dim, int(bool(m.parity)), int(ctx.sequential), len(m.h_sizes), m._hid,
+            masks.data_ptr(), rows, m.dim, int(bool(m.parity)), int(ctx.sequential), len(m.h_sizes), m._hid,
             _stream()))
         _lib.note_atomic_sums(f"{type(m).__name__}.backward", f"dim={m.dim}, hidden={m.h_sizes}")
         return grad_x, ret, None, None, None
@@ -1786,7 +1802,10 @@ class MAF(_TwoWayFlow):
     """Masked autoregressive flow (flows/maf.py:21-62): ``inverse`` is one pass of the MADE network (density
     estimation), ``forward`` decodes the elements one at a time (dim passes).  Same constructor, attribute names and
     state_dict keys (``net.{2l}.weight / .bias / .mask``) as the reference; each direction is one ``mnf_maf`` launch
-    (generic path: a thread per row, masked weights in LDS), gradients from ``mnf_maf_bwd``.  ``net`` must be a
+    (generic path: a thread per row, masked weights in LDS), gradients from ``mnf_maf_bwd``.  The one-pass direction
+    (``MAF.inverse``, ``IAF.forward``) has run-time-shaped matrix-core kernels as well (``mnf_maf_rt`` /
+    ``mnf_maf_bwd_rt``, families ``maf_rt`` / ``maf_bwd_rt``): ``_rt`` sends a call there -- see _dispatch.py,
+    ``MAF_RT_MIN_ROWS``; ``force_generic = 1 / 2`` forces the VALU / the run-time-shaped kernels.  ``net`` must be a
     ``MADE(dim, hidden, 2 * dim)``: the kernels evaluate the masked network themselves."""
 
     _sequential_forward = True  # IAF: the two directions swapped
@@ -1835,6 +1854,34 @@ class MAF(_TwoWayFlow):
             cached = self.__dict__["_order_cache"] = (key, bool(((conn != 0) & ~allowed).sum() == 0))
         return cached[1]
 
+    def _rt(self, rows: int, sequential: bool, bwd: bool = False) -> bool:
+        """Does this call go to the run-time-shaped matrix-core kernels?  The one-pass direction only; where
+        _dispatch.wants_rt says so (not under an fp32 request, never with force_generic = 1), from
+        _dispatch.MAF_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2 alone), and where the library has the shape."""
+        if sequential:
+            return False
+        force = int(self.force_generic)
+        if not _dispatch.wants_rt(rows, force, self._fp32_request()):
+            return False
+        if force != 2 and (_dispatch.MAF_RT_MIN_ROWS is None or rows < _dispatch.MAF_RT_MIN_ROWS):
+            return False
+        lib = _lib.load()
+        query = lib.mnf_maf_bwd_rt_supported if bwd else lib.mnf_maf_rt_supported
+        return bool(query(self.dim, len(self.h_sizes), self._hid))
+
+    def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, masks: Tensor, sequential: bool) -> None:
+        """One forward launch: mnf_maf_rt where _rt says so, else mnf_maf (an UNSUPPORTED answer of the former too)."""
+        lib, rows = _lib.load(), x.shape[0]
+        if self._rt(rows, sequential):
+            rc = lib.mnf_maf_rt(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(),
+                                rows, self.dim, int(bool(self.parity)), len(self.h_sizes), self._hid, _stream())
+            if rc != _lib.MNF_ERR_UNSUPPORTED:
+                _lib.check("mnf_maf_rt", rc)
+                return
+        _lib.check("mnf_maf", lib.mnf_maf(
+            x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(), rows, self.dim,
+            int(bool(self.parity)), int(sequential), len(self.h_sizes), self._hid, _stream()))
+
     def _run(self, x, inverse, accum):
         sequential = bool(inverse) != self._sequential_forward
         if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
@@ -1864,9 +1911,7 @@ class MAF(_TwoWayFlow):
         masks = self._mask_bytes(x.device)
         y = torch.empty_like(x)
         ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_maf", _lib.load().mnf_maf(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), int(accum is not None), flat.data_ptr(), masks.data_ptr(),
-            x.shape[0], self.dim, int(bool(self.parity)), int(sequential), len(self.h_sizes), self._hid, _stream()))
+        self._launch(x, y, ld, int(accum is not None), flat, masks, sequential)
         return y, (None if accum is not None else ld)
 
 
