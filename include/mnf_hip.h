@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 21
+#define MNF_ABI_VERSION 22
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -465,6 +465,22 @@ int64_t mnf_maf_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const 
 int mnf_maf_bwd_rt_det(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
                        const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim, int parity,
                        int n_hidden, const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
+/* The ELEMENT-BY-ELEMENT direction (mnf_maf's sequential = 1: MAF.forward, IAF.inverse, torch_mnf/flows/maf.py:39-51) on
+ * the f16 matrix pipe (mnf_maf_rt.hip, kernel family maf_seq_rt): per 16-row tile dim evaluations of the masked net on the
+ * partially decoded row (elements not yet decoded are exactly 0, maf.py:43-50: right for any MADE), y_i = (z_i - t_i) e^{-s_i}
+ * with z the input, flipped when `parity`; log_det = -sum s_i.  Same flat / masks / parity / log_det conventions and the
+ * same masked-weight rules as mnf_maf_rt.  Shapes: mnf_maf_rt's whose converted net stays resident in LDS (at most 150 KB)
+ * next to a slab of 16 x dim floats for each of 8, 4, 2 or 1 waves within 160 KB -- mnf_maf_seq_rt_supported, host only, the
+ * launcher's own plan; a streaming plan of mnf_maf_rt has no launch here.  MNF_ERR_INVALID_ARG (before any launch): a NULL
+ * x / y / flat / masks, x == y, rows < 0, dim < 1, n_hidden < 1, a NULL or non-positive hidden.  rows == 0: MNF_OK, nothing
+ * is launched, no device needed.  A shape outside the plan: MNF_ERR_UNSUPPORTED (the caller runs mnf_maf).  log_det may be
+ * NULL.  Gradients of this direction: mnf_maf_bwd (it needs x and y only). */
+int mnf_maf_seq_rt_supported(int dim, int n_hidden, const int* hidden_host);
+/* Workgroups of the mnf_maf_seq_rt launch of `rows` rows (a persistent grid: workgroup b takes the blocks of 16 x waves rows
+ * b, b + grid, ...); 0: nothing to launch, a shape outside the plan, or no gfx950 device visible. */
+int64_t mnf_maf_seq_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden_host);
+int mnf_maf_seq_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
+                   int64_t rows, int dim, int parity, int n_hidden, const int* hidden_host, void* stream);
 
 /* ------------------------------------------------ MNFLinear.forward behind the flow path
  * torch_mnf/layers/mnf_linear.py:46-56 with z (rows, n_in) = what sample_z's last flow wrote:
@@ -826,7 +842,8 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  *   mnf_rnvp_rt_supported             >= 1 conditioner layer, widths 4 .. 256, any dim
  *   mnf_rnvp_bwd_rt_supported         1 .. 4 conditioner layers of widths 4 .. 128, any dim
  *   mnf_maf_rt_supported              (declared with mnf_maf_rt) >= 1 hidden layer, widths 4 .. 128, any dim
- *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim */
+ *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim
+ *   mnf_maf_seq_rt_supported          (declared with mnf_maf_seq_rt) mnf_maf_rt's shapes whose net stays resident in LDS */
 int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);

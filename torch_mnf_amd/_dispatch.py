@@ -49,7 +49,9 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything                                          | maf_generic (VALU)             |
 | MAF.inverse / IAF.forward bwd | >= MAF_RT_MIN_ROWS | 1..4 hidden layers of widths 4..64, any d     | maf_bwd_rt                     |
 |                          | else            | anything                                          | maf_bwd_generic (VALU, atomics) |
-| MAF.forward / IAF.inverse, both passes | any | anything (element by element)                    | maf_generic / maf_bwd_generic  |
+| MAF.forward / IAF.inverse fwd | >= MAF_SEQ_RT_MIN_ROWS | maf_rt's shapes whose net stays resident in LDS   | maf_seq_rt                     |
+|                          | else            | anything (element by element)                     | maf_generic (VALU)             |
+| MAF.forward / IAF.inverse bwd | any        | anything (element by element)                     | maf_bwd_generic (VALU, atomics) |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -134,6 +136,15 @@ GLOW_ACTNORM_RT = False
 # mean opt-in: only a layer's force_generic = 2 reaches the kernels.
 MAF_RT_MIN_ROWS = 2048
 
+# MAF / IAF, the element-by-element direction (MAF.forward, IAF.inverse: sampling from a MAF, the density of an IAF) on the
+# matrix-core kernel maf_seq_rt (csrc/mnf_maf_rt.hip; flows.MAF._rt_seq), forward launches only: by the rule
+# above MAF_RT_MIN_ROWS -- the smallest of the measured row counts (2,048 / 8,192 / 65,536 at (dim, hidden) = (2, 24x3),
+# (6, 16x2), (64, 24x3), (64, 64x2)) from which it is not slower than the VALU kernel for every timed shape, never below
+# RT_MIN_ROWS (tools/time_maf_seq_rt.py, profiles/r15/maf_seq_rt_ab.txt).  It wins every cell, the narrowest one being
+# (6, 16x2) at 65,536 rows, 1.13 against 1.99 ns per row (at 2,048 rows: 25 against 63); (64, 64x2) at 65,536 rows: 10.8
+# against 1,575.  None would mean opt-in: only a layer's force_generic = 2 reaches the kernel.
+MAF_SEQ_RT_MIN_ROWS = 2048
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -179,13 +190,18 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
-    "nsf" | "rnvp" | "glow" | "maf", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
+    "nsf" | "rnvp" | "glow" | "maf" | "maf_seq", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
     Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
-    MAF / IAF, hidden = MADE's hidden sizes -- the element-by-element direction is "valu" always)."""
+    MAF / IAF, hidden = MADE's hidden sizes; "maf_seq": their element-by-element direction, whose "bwd" is "valu"
+    always)."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
+    if kind == "maf_seq":  # the element-by-element direction: a matrix-core forward kernel, gradients on the VALU kernel
+        if direction != "fwd" or MAF_SEQ_RT_MIN_ROWS is None or rows < MAF_SEQ_RT_MIN_ROWS or not wants_rt(rows):
+            return "valu"
+        return "rt" if lib.mnf_maf_seq_rt_supported(dim, n, hid) else "valu"
     if kind == "maf":
         if MAF_RT_MIN_ROWS is None or rows < MAF_RT_MIN_ROWS or not wants_rt(rows):
             return "valu"

@@ -1749,7 +1749,8 @@ class RNVP(_HipFlow):
 
 class _MafFn(torch.autograd.Function):
     """MAF / IAF with gradients (mnf_maf / mnf_maf_bwd; the one-pass direction on mnf_maf_rt / mnf_maf_bwd_rt where
-    MAF._rt says so).  ``home``: see _RnvpFn."""
+    MAF._rt says so, the element-by-element forward on mnf_maf_seq_rt where MAF._rt_seq does -- its backward is
+    mnf_maf_bwd always).  ``home``: see _RnvpFn."""
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, sequential, home=None):
@@ -1805,7 +1806,10 @@ class MAF(_TwoWayFlow):
     (generic path: a thread per row, masked weights in LDS), gradients from ``mnf_maf_bwd``.  The one-pass direction
     (``MAF.inverse``, ``IAF.forward``) has run-time-shaped matrix-core kernels as well (``mnf_maf_rt`` /
     ``mnf_maf_bwd_rt``, families ``maf_rt`` / ``maf_bwd_rt``): ``_rt`` sends a call there -- see _dispatch.py,
-    ``MAF_RT_MIN_ROWS``; ``force_generic = 1 / 2`` forces the VALU / the run-time-shaped kernels.  ``net`` must be a
+    ``MAF_RT_MIN_ROWS``; ``force_generic = 1 / 2`` forces the VALU / the run-time-shaped kernels.  The element-by-element
+    direction (``MAF.forward``, ``IAF.inverse``) has a matrix-core forward kernel too (``mnf_maf_seq_rt``, family
+    ``maf_seq_rt``: dim net evaluations per 16-row tile, nets that stay resident in LDS): ``_rt_seq`` sends a call there
+    -- ``_dispatch.MAF_SEQ_RT_MIN_ROWS``; its gradients stay on ``mnf_maf_bwd``.  ``net`` must be a
     ``MADE(dim, hidden, 2 * dim)``: the kernels evaluate the masked network themselves."""
 
     _sequential_forward = True  # IAF: the two directions swapped
@@ -1869,14 +1873,28 @@ class MAF(_TwoWayFlow):
         query = lib.mnf_maf_bwd_rt_supported if bwd else lib.mnf_maf_rt_supported
         return bool(query(self.dim, len(self.h_sizes), self._hid))
 
+    def _rt_seq(self, rows: int) -> bool:
+        """Does an element-by-element call (MAF.forward, IAF.inverse) go to the matrix-core kernel maf_seq_rt?  As _rt:
+        where _dispatch.wants_rt says so, from _dispatch.MAF_SEQ_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2
+        alone), and where the library has the shape (a net that stays resident in LDS).  Forward launches only: the
+        gradients of this direction stay on mnf_maf_bwd."""
+        force = int(self.force_generic)
+        if not _dispatch.wants_rt(rows, force, self._fp32_request()):
+            return False
+        if force != 2 and (_dispatch.MAF_SEQ_RT_MIN_ROWS is None or rows < _dispatch.MAF_SEQ_RT_MIN_ROWS):
+            return False
+        return bool(_lib.load().mnf_maf_seq_rt_supported(self.dim, len(self.h_sizes), self._hid))
+
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, masks: Tensor, sequential: bool) -> None:
-        """One forward launch: mnf_maf_rt where _rt says so, else mnf_maf (an UNSUPPORTED answer of the former too)."""
+        """One forward launch: mnf_maf_rt / mnf_maf_seq_rt where _rt / _rt_seq says so, else mnf_maf (an UNSUPPORTED
+        answer of the former too)."""
         lib, rows = _lib.load(), x.shape[0]
-        if self._rt(rows, sequential):
-            rc = lib.mnf_maf_rt(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(),
-                                rows, self.dim, int(bool(self.parity)), len(self.h_sizes), self._hid, _stream())
+        name = "mnf_maf_seq_rt" if sequential else "mnf_maf_rt"
+        if self._rt_seq(rows) if sequential else self._rt(rows, False):
+            rc = getattr(lib, name)(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(),
+                                    rows, self.dim, int(bool(self.parity)), len(self.h_sizes), self._hid, _stream())
             if rc != _lib.MNF_ERR_UNSUPPORTED:
-                _lib.check("mnf_maf_rt", rc)
+                _lib.check(name, rc)
                 return
         _lib.check("mnf_maf", lib.mnf_maf(
             x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(), rows, self.dim,
@@ -1917,7 +1935,8 @@ class MAF(_TwoWayFlow):
 
 class IAF(MAF):
     """Inverse autoregressive flow (flows/maf.py:65-72): MAF with ``forward`` and ``inverse`` swapped -- one pass to
-    sample, dim passes to evaluate a density."""
+    sample, dim passes to evaluate a density (``IAF.inverse`` is the same launch as ``MAF.forward``: ``maf_seq_rt`` where
+    ``MAF._rt_seq`` says so)."""
 
     _sequential_forward = False
 
