@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 22
+#define MNF_ABI_VERSION 23
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -481,6 +481,38 @@ int mnf_maf_seq_rt_supported(int dim, int n_hidden, const int* hidden_host);
 int64_t mnf_maf_seq_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden_host);
 int mnf_maf_seq_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
                    int64_t rows, int dim, int parity, int n_hidden, const int* hidden_host, void* stream);
+/* Gradients of the ELEMENT-BY-ELEMENT direction on the f16 matrix pipe (mnf_maf_seq_bwd_rt.hip, kernel family
+ * maf_seq_bwd_rt), for masks that are autoregressive in index order (as mnf_maf_bwd, sequential = 1).  One
+ * call is the whole gradient: (1) the solve launch -- the net once on y, then for i = dim-1 .. 0 the total cotangent G_i,
+ * grad_x[i'] = G_i e^{-s_i} (i' = dim-1-i when parity) and the one-hot pair (-(G_i y_i) - grad_ld, -G_i e^{-s_i}) back
+ * through the masked net into G_j, j < i; it leaves cot[i] = -G_i e^{-s_i} and -grad_ld in the workspace; (2) with
+ * grad_flat != NULL, mnf_affine_half_grad_scale on (cot, -grad_ld) and (3) mnf_maf_bwd_rt (the _det entry:
+ * mnf_maf_bwd_rt_det) with x = y, grad_y = cot, grad_ld = -grad_ld, parity = 0, whose parameter gradients are this
+ * direction's (its grad_x goes to workspace scratch).  y = the forward call's output; grad_x is written, grad_flat ADDED to
+ * (or NULL); grad_y / grad_ld may be NULL; grad_scale_dev as mnf_maf_bwd_rt.  A masked-out weight is staged as exactly 0 by
+ * a select and its grad_flat entry receives no add.
+ *   shapes      mnf_maf_bwd_rt's (1 .. 4 hidden layers of widths 4 .. 64) whose LDS plan fits 160 KB: the converted net
+ *               with the s head of the last MaskedLinear, the transposed blocks of the first and the hidden layers, the
+ *               last MaskedLinear as 2 dim fp32 rows, and two slabs of 16 x dim floats (padded to 16 columns) for each of
+ *               8, 4, 2 or 1 waves -- mnf_maf_seq_bwd_rt_supported, host only, the launcher's own plan.
+ *   workspace   floats: mnf_maf_seq_bwd_rt_workspace(rows, dim) = cot + the weight pass's discarded grad_x + -grad_ld + one
+ *               scale; the _det entry: mnf_maf_seq_bwd_rt_det_workspace = that + mnf_maf_bwd_rt_det_workspace's slots.
+ *               0 for rows < 1.
+ * MNF_ERR_INVALID_ARG (before any launch): a NULL y / grad_x / flat / masks / grad_scale_dev / workspace, a workspace that is
+ * too small, y == grad_x, grad_y == grad_x, grad_flat == flat, rows < 0, dim < 1, n_hidden < 1, a NULL or non-positive
+ * hidden.  rows == 0: MNF_OK, nothing is launched, no device needed.  A shape outside the plan: MNF_ERR_UNSUPPORTED (the
+ * caller runs mnf_maf_bwd).  mnf_maf_seq_bwd_rt refuses (MNF_ERR_UNSUPPORTED) when MNF_DETERMINISTIC is set; the _det entry
+ * does not: the solve has no sums, and its weight pass adds them in a fixed order. */
+int mnf_maf_seq_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host);
+int64_t mnf_maf_seq_bwd_rt_workspace(int64_t rows, int dim);
+int64_t mnf_maf_seq_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host);
+int mnf_maf_seq_bwd_rt(const float* y, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                       const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim, int parity,
+                       int n_hidden, const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
+int mnf_maf_seq_bwd_rt_det(const float* y, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                           const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim,
+                           int parity, int n_hidden, const int* hidden_host, float* workspace, int64_t workspace_floats,
+                           void* stream);
 
 /* ------------------------------------------------ MNFLinear.forward behind the flow path
  * torch_mnf/layers/mnf_linear.py:46-56 with z (rows, n_in) = what sample_z's last flow wrote:

@@ -51,7 +51,8 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything                                          | maf_bwd_generic (VALU, atomics) |
 | MAF.forward / IAF.inverse fwd | >= MAF_SEQ_RT_MIN_ROWS | maf_rt's shapes whose net stays resident in LDS   | maf_seq_rt                     |
 |                          | else            | anything (element by element)                     | maf_generic (VALU)             |
-| MAF.forward / IAF.inverse bwd | any        | anything (element by element)                     | maf_bwd_generic (VALU, atomics) |
+| MAF.forward / IAF.inverse bwd | >= MAF_SEQ_BWD_RT_MIN_ROWS (opt-in: None) | maf_bwd_rt's shapes whose solve plan fits LDS | maf_seq_bwd_rt |
+|                          | else            | anything (element by element)                     | maf_bwd_generic (VALU, atomics) |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -145,6 +146,20 @@ MAF_RT_MIN_ROWS = 2048
 # against 1,575.  None would mean opt-in: only a layer's force_generic = 2 reaches the kernel.
 MAF_SEQ_RT_MIN_ROWS = 2048
 
+# MAF / IAF, the gradients of the element-by-element direction (what an IAF is trained through: IAF.inverse is its density
+# pass) on the matrix cores (csrc/mnf_maf_seq_bwd_rt.hip, family maf_seq_bwd_rt; flows.MAF._rt_seq_bwd, DESIGN.md 3.8g: a
+# triangular solve for the total cotangents, then the one-pass direction's weight pass maf_bwd_rt at the decoded output):
+# OPT-IN.  None: every call stays on maf_bwd_generic, force_generic = 2 included (existing tests pin that kernel under
+# force_generic = 2); a number sends a call there from that many rows on where _dispatch.wants_rt says so -- so never below
+# RT_MIN_ROWS unless the layer's force_generic = 2 lifts that floor, never with force_generic = 1 -- and where
+# mnf_maf_seq_bwd_rt_supported has the shape.  Under MNF_DETERMINISTIC=1 the route runs mnf_maf_seq_bwd_rt_det (no atomic
+# sums).  Measured (tools/time_maf_seq_bwd_rt.py, profiles/r16/maf_seq_bwd_rt_ab.txt: forward + backward, this route against
+# maf_bwd_generic, at (dim, hidden) = (2, 24x3), (6, 16x2), (64, 24x3), (64, 64x2) and 2,048 / 8,192 / 65,536 rows, the fixed-order
+# form too at 65,536): the route wins every cell, the narrowest being (2, 24x3) at 2,048 rows, 212 against 288 ns per row;
+# (64, 64x2) at 65,536 rows: 29.3 against 11,990.  The smallest row count from which it wins every cell is 2,048 = RT_MIN_ROWS:
+# the value a follow-up that may edit the pinned tests would make the default.
+MAF_SEQ_BWD_RT_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -193,13 +208,17 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     "nsf" | "rnvp" | "glow" | "maf" | "maf_seq", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
     Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
     MAF / IAF, hidden = MADE's hidden sizes; "maf_seq": their element-by-element direction, whose "bwd" is "valu"
-    always)."""
+    unless MAF_SEQ_BWD_RT_MIN_ROWS is set)."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
-    if kind == "maf_seq":  # the element-by-element direction: a matrix-core forward kernel, gradients on the VALU kernel
-        if direction != "fwd" or MAF_SEQ_RT_MIN_ROWS is None or rows < MAF_SEQ_RT_MIN_ROWS or not wants_rt(rows):
+    if kind == "maf_seq" and direction != "fwd":  # its gradients: the VALU kernel unless the rt route is opted in
+        if MAF_SEQ_BWD_RT_MIN_ROWS is None or rows < MAF_SEQ_BWD_RT_MIN_ROWS or not wants_rt(rows):
+            return "valu"
+        return "rt" if lib.mnf_maf_seq_bwd_rt_supported(dim, n, hid) else "valu"
+    if kind == "maf_seq":  # the element-by-element direction: a matrix-core forward kernel
+        if MAF_SEQ_RT_MIN_ROWS is None or rows < MAF_SEQ_RT_MIN_ROWS or not wants_rt(rows):
             return "valu"
         return "rt" if lib.mnf_maf_seq_rt_supported(dim, n, hid) else "valu"
     if kind == "maf":

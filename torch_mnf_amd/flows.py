@@ -1750,7 +1750,7 @@ class RNVP(_HipFlow):
 class _MafFn(torch.autograd.Function):
     """MAF / IAF with gradients (mnf_maf / mnf_maf_bwd; the one-pass direction on mnf_maf_rt / mnf_maf_bwd_rt where
     MAF._rt says so, the element-by-element forward on mnf_maf_seq_rt where MAF._rt_seq does -- its backward is
-    mnf_maf_bwd always).  ``home``: see _RnvpFn."""
+    mnf_maf_seq_bwd_rt where MAF._rt_seq_bwd says so (opt-in), else mnf_maf_bwd).  ``home``: see _RnvpFn."""
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, sequential, home=None):
@@ -1791,6 +1791,22 @@ class _MafFn(torch.autograd.Function):
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_maf_bwd_rt", rc)
                 return grad_x, ret, None, None, None
+        if ctx.sequential and m._rt_seq_bwd(rows):
+            # the element-by-element direction on the matrix cores: the solve for the total cotangents, then the one-pass
+            # direction's weight pass at the decoded output (one library call)
+            scale = _grad_scale(gy, gl, rows, m.dim, x.device)
+            det = _lib.deterministic()  # fixed-order sums: the weight pass's slots behind the call's own workspace
+            n_ws = (lib.mnf_maf_seq_bwd_rt_det_workspace(rows, m.dim, len(m.h_sizes), m._hid) if det
+                    else lib.mnf_maf_seq_bwd_rt_workspace(rows, m.dim))
+            if n_ws > 0:
+                ws = torch.empty(n_ws, dtype=torch.float32, device=x.device)
+                entry = lib.mnf_maf_seq_bwd_rt_det if det else lib.mnf_maf_seq_bwd_rt
+                rc = entry(y.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
+                           masks.data_ptr(), scale.data_ptr(), rows, m.dim, int(bool(m.parity)), len(m.h_sizes), m._hid,
+                           ws.data_ptr(), n_ws, _stream())
+                if rc != _lib.MNF_ERR_UNSUPPORTED:
+                    _lib.check("mnf_maf_seq_bwd_rt", rc)
+                    return grad_x, ret, None, None, None
         _lib.check("mnf_maf_bwd", lib.mnf_maf_bwd(
             x.data_ptr(), y.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
             masks.data_ptr(), rows, m.dim, int(bool(m.parity)), int(ctx.sequential), len(m.h_sizes), m._hid,
@@ -1809,7 +1825,8 @@ class MAF(_TwoWayFlow):
     ``MAF_RT_MIN_ROWS``; ``force_generic = 1 / 2`` forces the VALU / the run-time-shaped kernels.  The element-by-element
     direction (``MAF.forward``, ``IAF.inverse``) has a matrix-core forward kernel too (``mnf_maf_seq_rt``, family
     ``maf_seq_rt``: dim net evaluations per 16-row tile, nets that stay resident in LDS): ``_rt_seq`` sends a call there
-    -- ``_dispatch.MAF_SEQ_RT_MIN_ROWS``; its gradients stay on ``mnf_maf_bwd``.  ``net`` must be a
+    -- ``_dispatch.MAF_SEQ_RT_MIN_ROWS``; its gradients stay on ``mnf_maf_bwd`` unless ``_rt_seq_bwd`` sends them to
+    ``mnf_maf_seq_bwd_rt`` (family ``maf_seq_bwd_rt``; opt-in, ``_dispatch.MAF_SEQ_BWD_RT_MIN_ROWS``).  ``net`` must be a
     ``MADE(dim, hidden, 2 * dim)``: the kernels evaluate the masked network themselves."""
 
     _sequential_forward = True  # IAF: the two directions swapped
@@ -1884,6 +1901,18 @@ class MAF(_TwoWayFlow):
         if force != 2 and (_dispatch.MAF_SEQ_RT_MIN_ROWS is None or rows < _dispatch.MAF_SEQ_RT_MIN_ROWS):
             return False
         return bool(_lib.load().mnf_maf_seq_rt_supported(self.dim, len(self.h_sizes), self._hid))
+
+    def _rt_seq_bwd(self, rows: int) -> bool:
+        """Do the gradients of an element-by-element call go to the matrix-core route maf_seq_bwd_rt?  Opt-in: only with
+        _dispatch.MAF_SEQ_BWD_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not select it), from that many
+        rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1 vetoes, as does an fp32
+        request) and where the library has the shape."""
+        floor = _dispatch.MAF_SEQ_BWD_RT_MIN_ROWS
+        if floor is None or rows < floor:
+            return False
+        if not _dispatch.wants_rt(rows, int(self.force_generic), self._fp32_request()):
+            return False
+        return bool(_lib.load().mnf_maf_seq_bwd_rt_supported(self.dim, len(self.h_sizes), self._hid))
 
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, masks: Tensor, sequential: bool) -> None:
         """One forward launch: mnf_maf_rt / mnf_maf_seq_rt where _rt / _rt_seq says so, else mnf_maf (an UNSUPPORTED
