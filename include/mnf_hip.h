@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 23
+#define MNF_ABI_VERSION 24
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -400,6 +400,22 @@ int64_t mnf_nsf_ar_flat_floats(int dim, int K, int n_hidden, const int* hidden_h
 int mnf_nsf_ar_bwd(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
                    const float* flat, int64_t rows, int dim, int K, float tail_bound, int inverse, int n_hidden,
                    const int* hidden_host, void* stream);
+/* The ONE-PASS direction (mnf_nsf_ar's inverse = 1: NSF_AR.inverse, x -> z, spline_flow.py:218-235 -- what log_prob and
+ * training run through) on the f16 matrix pipe (mnf_nsf_ar_rt.hip, kernel family nsf_ar_rt): every
+ * conditioner reads the input, so the elements are independent -- four consecutive elements' nets run side by side as one
+ * block-diagonal net per 16-row tile, weights read from `flat` in mnf_nsf_ar's layout (no operand image), then the spline
+ * forward.  Same flat / tail_bound / log_det conventions as mnf_nsf_ar.  Shapes (mnf_nsf_ar_rt_supported, host only, the
+ * launcher's own plan): dim >= 2 (dim = 1 has no net), K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 16, flat below 2^31
+ * floats.  MNF_ERR_INVALID_ARG (before any launch): a NULL x / y / flat, x == y, rows < 0, dim < 1, K < 1, tail_bound <= 0,
+ * a NULL or non-positive hidden.  rows == 0: MNF_OK, nothing is launched, no device needed.  A shape outside the plan:
+ * MNF_ERR_UNSUPPORTED (the caller runs mnf_nsf_ar).  log_det may be NULL.  Rows holding non-finite values: NaN from the
+ * group of four elements on that holds the first one.  Gradients of this direction: mnf_nsf_ar_bwd (it recomputes from x). */
+int mnf_nsf_ar_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);
+/* Workgroups of the mnf_nsf_ar_rt launch of `rows` rows (a persistent grid: workgroup b takes the blocks of 16 x tiles x waves
+ * rows b, b + grid, ...); 0: nothing to launch, a shape outside the plan, or no gfx950 device visible. */
+int64_t mnf_nsf_ar_rt_grid(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_nsf_ar_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim, int K,
+                  float tail_bound, int n_hidden, const int* hidden_host, void* stream);
 
 /* ------------------------------------------------------------------ Glow: the d x d parameter preparation
  * torch_mnf/flows/glow.py:20-37.  out = W = P (tril(L,-1) + I) (triu(U,1) + diag(S)) (inverse = 0) or its inverse
@@ -875,7 +891,8 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  *   mnf_rnvp_bwd_rt_supported         1 .. 4 conditioner layers of widths 4 .. 128, any dim
  *   mnf_maf_rt_supported              (declared with mnf_maf_rt) >= 1 hidden layer, widths 4 .. 128, any dim
  *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim
- *   mnf_maf_seq_rt_supported          (declared with mnf_maf_seq_rt) mnf_maf_rt's shapes whose net stays resident in LDS */
+ *   mnf_maf_seq_rt_supported          (declared with mnf_maf_seq_rt) mnf_maf_rt's shapes whose net stays resident in LDS
+ *   mnf_nsf_ar_rt_supported           (declared with mnf_nsf_ar_rt) K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 16, dim >= 2 */
 int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);

@@ -53,6 +53,9 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything (element by element)                     | maf_generic (VALU)             |
 | MAF.forward / IAF.inverse bwd | >= MAF_SEQ_BWD_RT_MIN_ROWS (opt-in: None) | maf_bwd_rt's shapes whose solve plan fits LDS | maf_seq_bwd_rt |
 |                          | else            | anything (element by element)                     | maf_bwd_generic (VALU, atomics) |
+| NSF_AR.inverse fwd       | >= NSF_AR_RT_MIN_ROWS (opt-in: None) | d >= 2, K 2..16, 1..4 hidden layers of widths 4..16 | nsf_ar_rt |
+|                          | else            | anything                                          | nsf_ar_generic (VALU)          |
+| NSF_AR.forward fwd, NSF_AR bwd | any       | anything                                          | nsf_ar(_bwd)_generic (VALU)    |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -160,6 +163,19 @@ MAF_SEQ_RT_MIN_ROWS = 2048
 # the value a follow-up that may edit the pinned tests would make the default.
 MAF_SEQ_BWD_RT_MIN_ROWS = None
 
+# NSF_AR, the one-pass direction (NSF_AR.inverse: x -> z, what log_prob and training run through) on the matrix-core kernel
+# nsf_ar_rt (csrc/mnf_nsf_ar_rt.hip; flows.NSF_AR._rt), forward launches only: OPT-IN.  None: only a layer's
+# force_generic = 2 reaches the kernel (an existing test runs this direction above RT_MIN_ROWS and pins the VALU kernel); a
+# number sends a call there from that many rows on where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless
+# force_generic = 2 lifts that floor, never with force_generic = 1 or under an fp32 request -- and where
+# mnf_nsf_ar_rt_supported has the shape.  Measured (tools/time_nsf_ar_rt.py, profiles/r17/nsf_ar_rt_ab.txt: NSF_AR.inverse
+# through the layer, nsf_ar_rt against nsf_ar_generic, at (dim, K, n_h) = (2, 8, 16), (6, 5, 8), (16, 8, 8), (64, 5, 8),
+# (64, 8, 16) and 2,048 / 8,192 / 65,536 / 262,144 rows): the kernel wins all twenty cells, the narrowest being
+# (2, 8, 16) at 2,048 rows, 19.3 against 23.0 ns per row (1.19 x; at 262,144 rows 0.34 against 0.61); (64, 8, 16) at 262,144
+# rows: 5.80 against 57.0.  The smallest row count from which it wins every cell is 2,048 = RT_MIN_ROWS: the value a
+# follow-up that may edit the pinned test would make the default.
+NSF_AR_RT_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -205,14 +221,19 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
-    "nsf" | "rnvp" | "glow" | "maf" | "maf_seq", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
+    "nsf" | "rnvp" | "glow" | "maf" | "maf_seq" | "nsf_ar", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
     Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
     MAF / IAF, hidden = MADE's hidden sizes; "maf_seq": their element-by-element direction, whose "bwd" is "valu"
-    unless MAF_SEQ_BWD_RT_MIN_ROWS is set)."""
+    unless MAF_SEQ_BWD_RT_MIN_ROWS is set; "nsf_ar": NSF_AR with K and hidden = its nets' hidden widths -- "fwd" is the
+    one-pass direction NSF_AR.inverse, "valu" unless NSF_AR_RT_MIN_ROWS is set; "bwd" is "valu")."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
+    if kind == "nsf_ar":  # the one-pass direction's forward kernel is opt-in; no gradient kernel
+        if direction != "fwd" or NSF_AR_RT_MIN_ROWS is None or rows < NSF_AR_RT_MIN_ROWS or not wants_rt(rows):
+            return "valu"
+        return "rt" if lib.mnf_nsf_ar_rt_supported(dim, K, n, hid) else "valu"
     if kind == "maf_seq" and direction != "fwd":  # its gradients: the VALU kernel unless the rt route is opted in
         if MAF_SEQ_BWD_RT_MIN_ROWS is None or rows < MAF_SEQ_BWD_RT_MIN_ROWS or not wants_rt(rows):
             return "valu"

@@ -1485,9 +1485,7 @@ class _NsfArFn(torch.autograd.Function):
         flat = flat_with_grad.detach().contiguous()
         y = torch.empty_like(x)
         ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_nsf_ar", _lib.load().mnf_nsf_ar(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), 0, flat.data_ptr(), x.shape[0], module.dim, module.K,
-            float(module.B), int(inverse), len(module.h_sizes), module._hid, _stream()))
+        module._launch(x, y, ld, 0, flat, inverse)
         ctx.module, ctx.inverse = module, inverse
         ctx.save_for_backward(x, flat)
         return y, ld
@@ -1512,7 +1510,10 @@ class NSF_AR(_TwoWayFlow):
     parametrised by ``layers[i-1](first i elements)`` -- of the output in ``forward`` (sequential), of the input in
     ``inverse`` --, element 0 by ``init_param``.  Same constructor, attribute names and state_dict keys
     (``init_param``, ``layers.{i}.{0,2,4,6}.{weight,bias}``) as the reference; the arithmetic is one
-    ``mnf_nsf_ar`` launch per direction on the spline device function NSF_CL uses."""
+    ``mnf_nsf_ar`` launch per direction on the spline device function NSF_CL uses.  The one-pass direction
+    (``inverse``: x -> z, what ``log_prob`` and training run through) has a matrix-core forward kernel too
+    (``mnf_nsf_ar_rt``, family ``nsf_ar_rt``: four elements' nets side by side per 16-row tile): ``_rt`` sends a call there
+    -- ``_dispatch.NSF_AR_RT_MIN_ROWS``, opt-in as shipped; its gradients stay on ``mnf_nsf_ar_bwd``."""
 
     def __init__(self, dim: int, K: int = 5, B: float = 3, n_h: int = 8, net_class=MLP) -> None:
         super().__init__()
@@ -1532,6 +1533,32 @@ class NSF_AR(_TwoWayFlow):
     def _packed_params(self) -> list[Tensor]:
         return [self.init_param] + self._net_params(list(self.layers))
 
+    def _rt(self, rows: int) -> bool:
+        """Does a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_rt?  As MAF._rt_seq: where
+        _dispatch.wants_rt says so (never with force_generic = 1) and never under an fp32 request, from
+        _dispatch.NSF_AR_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2 alone), and where the library has the
+        shape.  Forward launches only: the gradients stay on mnf_nsf_ar_bwd, which recomputes from x."""
+        force = int(self.force_generic)
+        if self._fp32_request() or not _dispatch.wants_rt(rows, force, False):  # (split-f16 arithmetic: not even by name)
+            return False
+        if force != 2 and (_dispatch.NSF_AR_RT_MIN_ROWS is None or rows < _dispatch.NSF_AR_RT_MIN_ROWS):
+            return False
+        return bool(_lib.load().mnf_nsf_ar_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+
+    def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, inverse: bool) -> None:
+        """One forward launch: mnf_nsf_ar_rt where `inverse` and _rt says so, else mnf_nsf_ar (an UNSUPPORTED answer of
+        the former too)."""
+        lib, rows = _lib.load(), x.shape[0]
+        if inverse and self._rt(rows):
+            rc = lib.mnf_nsf_ar_rt(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), rows, self.dim,
+                                   self.K, float(self.B), len(self.h_sizes), self._hid, _stream())
+            if rc != _lib.MNF_ERR_UNSUPPORTED:
+                _lib.check("mnf_nsf_ar_rt", rc)
+                return
+        _lib.check("mnf_nsf_ar", lib.mnf_nsf_ar(
+            x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), rows, self.dim, self.K, float(self.B),
+            int(inverse), len(self.h_sizes), self._hid, _stream()))
+
     def _run(self, x, inverse, accum):
         if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
             xg = _grad_input(x)
@@ -1547,9 +1574,7 @@ class NSF_AR(_TwoWayFlow):
         flat, _ = self._packed(x.device)
         y = torch.empty_like(x)
         ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_nsf_ar", _lib.load().mnf_nsf_ar(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), int(accum is not None), flat.data_ptr(), x.shape[0], self.dim,
-            self.K, float(self.B), int(inverse), len(self.h_sizes), self._hid, _stream()))
+        self._launch(x, y, ld, int(accum is not None), flat, bool(inverse))
         return y, (None if accum is not None else ld)
 
 
