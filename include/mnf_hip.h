@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 24
+#define MNF_ABI_VERSION 25
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -416,6 +416,29 @@ int mnf_nsf_ar_rt_supported(int dim, int K, int n_hidden, const int* hidden_host
 int64_t mnf_nsf_ar_rt_grid(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
 int mnf_nsf_ar_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim, int K,
                   float tail_bound, int n_hidden, const int* hidden_host, void* stream);
+/* Gradients of the one-pass direction on the f16 matrix pipe (mnf_nsf_ar_bwd_rt.hip, kernel family nsf_ar_bwd_rt; DESIGN.md
+ * 3.8i): mnf_nsf_ar_bwd's inverse = 1 case with its argument order (no `inverse`) and its conventions -- grad_y / grad_ld may
+ * be NULL (a zero cotangent), grad_x is written, grad_flat is ADDED to (NULL: no parameter sums) -- recomputing from x as it
+ * does.  Per 16-row tile and group of four elements the block-diagonal net of mnf_nsf_ar_rt runs forwards keeping its hidden
+ * vectors, then the spline's derivative, the output layers' gradients and the delta chain over the diagonal blocks only; one
+ * staging exponent and one cotangent scale per launch (a power of two that every workgroup takes from a sample of grad_y /
+ * grad_ld: a mean() loss over 10^6 rows stays in range).  Shapes (mnf_nsf_ar_bwd_rt_supported, host only, the launcher's own
+ * plan): those of mnf_nsf_ar_rt with K = 5 or 8 (the compile-time list MNF_NSF_AR_BWD_KS).  MNF_ERR_INVALID_ARG (before any
+ * launch): a NULL x / grad_x / flat, x == grad_x, grad_y == grad_x, grad_flat == flat, rows < 0, dim < 1, K < 1,
+ * tail_bound <= 0, a NULL or non-positive hidden; _det with grad_flat and rows > 0: a NULL or too small workspace.  rows == 0:
+ * MNF_OK, nothing is launched, no device needed.  A shape outside the plan: MNF_ERR_UNSUPPORTED (the caller runs
+ * mnf_nsf_ar_bwd); mnf_nsf_ar_bwd_rt also under MNF_DETERMINISTIC=1, where its atomic sums are not wanted.
+ * mnf_nsf_ar_bwd_rt_det: the parameter sums in a fixed order -- every workgroup adds into a slot of its own in `workspace`
+ * (mnf_nsf_ar_bwd_rt_det_workspace floats: slots x the parameter count rounded up to 64; 0 without a gfx950 device, for
+ * rows < 1 or a shape outside the plan), the slots are added up in order: bit-identical sums run to run. */
+int mnf_nsf_ar_bwd_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_nsf_ar_bwd_rt(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                      const float* flat, int64_t rows, int dim, int K, float tail_bound, int n_hidden, const int* hidden_host,
+                      void* stream);
+int mnf_nsf_ar_bwd_rt_det(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                          const float* flat, int64_t rows, int dim, int K, float tail_bound, int n_hidden,
+                          const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
+int64_t mnf_nsf_ar_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
 
 /* ------------------------------------------------------------------ Glow: the d x d parameter preparation
  * torch_mnf/flows/glow.py:20-37.  out = W = P (tril(L,-1) + I) (triu(U,1) + diag(S)) (inverse = 0) or its inverse
@@ -892,7 +915,8 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  *   mnf_maf_rt_supported              (declared with mnf_maf_rt) >= 1 hidden layer, widths 4 .. 128, any dim
  *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim
  *   mnf_maf_seq_rt_supported          (declared with mnf_maf_seq_rt) mnf_maf_rt's shapes whose net stays resident in LDS
- *   mnf_nsf_ar_rt_supported           (declared with mnf_nsf_ar_rt) K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 16, dim >= 2 */
+ *   mnf_nsf_ar_rt_supported           (declared with mnf_nsf_ar_rt) K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 16, dim >= 2
+ *   mnf_nsf_ar_bwd_rt_supported       (declared with mnf_nsf_ar_bwd_rt) mnf_nsf_ar_rt's shapes with K = 5 or 8 */
 int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);

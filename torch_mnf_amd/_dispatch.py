@@ -55,7 +55,9 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything (element by element)                     | maf_bwd_generic (VALU, atomics) |
 | NSF_AR.inverse fwd       | >= NSF_AR_RT_MIN_ROWS (opt-in: None) | d >= 2, K 2..16, 1..4 hidden layers of widths 4..16 | nsf_ar_rt |
 |                          | else            | anything                                          | nsf_ar_generic (VALU)          |
-| NSF_AR.forward fwd, NSF_AR bwd | any       | anything                                          | nsf_ar(_bwd)_generic (VALU)    |
+| NSF_AR.inverse bwd       | >= NSF_AR_BWD_RT_MIN_ROWS (opt-in: None) | nsf_ar_rt's shapes with K = 5 or 8      | nsf_ar_bwd_rt                  |
+|                          | else            | anything                                          | nsf_ar_bwd_generic (VALU, atomics) |
+| NSF_AR.forward fwd / bwd | any             | anything (element by element)                     | nsf_ar(_bwd)_generic (VALU)    |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -176,6 +178,29 @@ MAF_SEQ_BWD_RT_MIN_ROWS = None
 # follow-up that may edit the pinned test would make the default.
 NSF_AR_RT_MIN_ROWS = None
 
+# NSF_AR, the gradients of the one-pass direction (every Adam step of an NSF_AR density model) on the matrix-core kernel
+# nsf_ar_bwd_rt (csrc/mnf_nsf_ar_bwd_rt.hip; flows.NSF_AR._rt_bwd): OPT-IN, with MAF_SEQ_BWD_RT_MIN_ROWS'
+# semantics.  None: every call stays on nsf_ar_bwd_generic, force_generic = 2 included (an existing test pins that kernel
+# under force_generic = 2); a number sends a call there from that many rows on where _dispatch.wants_rt says so -- never below
+# RT_MIN_ROWS unless force_generic = 2 lifts that floor, never with force_generic = 1 or under an fp32 request -- and where
+# mnf_nsf_ar_bwd_rt_supported has the shape (nsf_ar_rt's shapes with K = 5 or 8).  Under MNF_DETERMINISTIC=1 the route runs
+# mnf_nsf_ar_bwd_rt_det (no atomic sums).  Measured (tools/time_nsf_ar_bwd_rt.py, profiles/r18/nsf_ar_bwd_rt_ab.txt: NSF_AR.inverse +
+# backward through the layer, forward on nsf_ar_rt both times, this route against nsf_ar_bwd_generic, ns per row, at (dim, K,
+# n_h) = (2, 8, 16), (6, 5, 8), (16, 8, 8), (64, 5, 8), (64, 8, 16) and 2,048 / 8,192 / 65,536 / 262,144 rows, the fixed-order form
+# too at 65,536):
+#   (2, 8, 16)   90.0 against 89.3 | 21.9 / 21.9 | 6.75 / 8.31 | 4.67 / 7.07 | fixed order 7.07 / 9.51
+#   (6, 5, 8)    357 / 355         | 89.5 / 89.3 | 11.2 / 23.9 | 4.13 / 20.4 |             7.79 / 22.5
+#   (16, 8, 8)   602 / 602         | 150 / 150   | 19.6 / 68.2 | 8.96 / 63.6 |             19.8 / 68.5
+#   (64, 5, 8)   3,876 / 3,860     | 974 / 967   | 122 / 322   | 36.1 / 279  |             104 / 317
+#   (64, 8, 16)  3,882 / 3,896     | 578 / 927   | 89.4 / 430  | 59.5 / 413  |             124 / 446
+# At 65,536 and 262,144 rows the route wins all ten cells, the narrowest being (2, 8, 16) at 65,536 rows (6.75 against 8.31,
+# 1.23 x), the widest (64, 5, 8) at 262,144 (36.1 against 279, 7.7 x), and every fixed-order cell; no cell at 65,536 rows and
+# dim >= 16 is lost.  At 2,048 and 8,192 rows the step is bound by the layer's host side (packing dim - 1 nets' parameters:
+# ~180 us per call at dim 2, 7.9 ms at dim 64) and the routes tie to within 1 % (six cells 0.1-0.7 % behind: noise; (64, 8, 16)
+# at 8,192 rows 1.6 x ahead).  The smallest row count from which it wins every cell is 65,536: the value a follow-up that may
+# edit the pinned test would make the default.
+NSF_AR_BWD_RT_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -225,15 +250,18 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
     MAF / IAF, hidden = MADE's hidden sizes; "maf_seq": their element-by-element direction, whose "bwd" is "valu"
     unless MAF_SEQ_BWD_RT_MIN_ROWS is set; "nsf_ar": NSF_AR with K and hidden = its nets' hidden widths -- "fwd" is the
-    one-pass direction NSF_AR.inverse, "valu" unless NSF_AR_RT_MIN_ROWS is set; "bwd" is "valu")."""
+    one-pass direction NSF_AR.inverse, "valu" unless NSF_AR_RT_MIN_ROWS is set; "bwd" is its gradient pass, "valu" unless
+    NSF_AR_BWD_RT_MIN_ROWS is set)."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
-    if kind == "nsf_ar":  # the one-pass direction's forward kernel is opt-in; no gradient kernel
-        if direction != "fwd" or NSF_AR_RT_MIN_ROWS is None or rows < NSF_AR_RT_MIN_ROWS or not wants_rt(rows):
+    if kind == "nsf_ar":  # the one-pass direction's kernels are opt-in, the forward and the gradient one each by its own constant
+        floor = NSF_AR_RT_MIN_ROWS if direction == "fwd" else NSF_AR_BWD_RT_MIN_ROWS
+        if floor is None or rows < floor or not wants_rt(rows):
             return "valu"
-        return "rt" if lib.mnf_nsf_ar_rt_supported(dim, K, n, hid) else "valu"
+        query = lib.mnf_nsf_ar_rt_supported if direction == "fwd" else lib.mnf_nsf_ar_bwd_rt_supported
+        return "rt" if query(dim, K, n, hid) else "valu"
     if kind == "maf_seq" and direction != "fwd":  # its gradients: the VALU kernel unless the rt route is opted in
         if MAF_SEQ_BWD_RT_MIN_ROWS is None or rows < MAF_SEQ_BWD_RT_MIN_ROWS or not wants_rt(rows):
             return "valu"

@@ -60,30 +60,6 @@ struct MafSeqBwdArgs {
   NetDesc net;                  // dim -> h_1 .. h_n
 };
 
-namespace rt {
-
-// fp32 tiles -> split tiles with the row's power-of-two scale, UP as well as down: the row's largest entry goes to
-// [2^12, 2^13) (mnf_rt_bwd.h split_rows only scales down; a one-hot cotangent of a mean loss is ~1/rows and would sit in
-// f16's subnormals).  A row of zeros or non-finite values keeps scale 1.
-template <int MT_MAX>
-__device__ __forceinline__ void split_rows_both(const f32x4 (&v)[MT_MAX], Hidden<MT_MAX, 1>& h) {
-  float fm = 0.f;
-#pragma unroll
-  for (int m = 0; m < MT_MAX; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) fm = __builtin_fmaxf(fm, finite_abs(v[m][r]));
-  fm = max_over_q(fm);
-  int e = (int)((__builtin_bit_cast(uint32_t, fm) >> 23) & 0xffu) - 127 - 12;
-  e = fm > 0.f ? (e < -100 ? -100 : e) : 0;
-  const float down = pow2f(-e);
-  h.up[0] = pow2f(e);
-  float unused = 0.f;
-#pragma unroll
-  for (int m = 0; m < MT_MAX; ++m) split_tile(v[m] * down, h.hi[0][m], h.lo[0][m], unused);
-}
-
-}  // namespace rt
-
 // The workgroup's images: every segment's blocks dealt out over the waves, one block per trip (masked by a select, scaled by
 // wdown, element-by-element loads at clamped indices: once per workgroup), and the forward layers' bias tiles as plain fp32.
 __device__ __forceinline__ void maf_seq_bwd_stage(const MafSeqBwdArgs& a, uint32_t* blocks, float* bias, float wdown) {

@@ -185,6 +185,58 @@ __device__ __forceinline__ void dw_phase(const Exchange& exa, int a0, int MA, co
   dw_phase_rows(exa, a0, MA, exb, b0, MB, sa, sb, nw, out_scale, gW, gb, ContigRows{m0, n_out}, n_in, n0, keep...);
 }
 
+// The same products for weights that do not form ONE row-major matrix (NSF_AR's four nets side by side: a block-diagonal
+// layer whose blocks lie in four places of `flat`): the entry of (delta tile m, unit u) against input column k = 16 (n0 + n)
+// + i is added at g + at.w(m, u, k), its bias at g + at.b(m, u); a negative offset DROPS the add (an off-diagonal block, a
+// padding unit: exactly no add, as with MaskKeep).  bias: this phase adds the bias sums (with the input tile n = 0).  The
+// (m, n) pairs go to the waves by shape alone, as above.
+template <typename At>
+__device__ __forceinline__ void dw_phase_at(const Exchange& exa, int a0, int MA, const Exchange& exb, int b0, int MB,
+                                            const float* sa, const float* sb, int nw, float out_scale, float* __restrict__ g,
+                                            const At& at, bool bias, int n0) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, q = lane >> 4;
+  const int us = exa.unit_stride();
+  f16x4 ones;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ones[e] = (_Float16)1.f;
+  const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+  int m = 0, n = wave;  // pair index t = m * MB + n, dealt out round robin
+  for (int t = wave; t < MA * MB; t += nw) {
+    while (n >= MB) {
+      n -= MB;
+      ++m;
+    }
+    const uint16_t* pa = exa.tile(a0 + m) + i * us + 4 * q;
+    const uint16_t* pb = exb.tile(b0 + n) + i * us + 4 * q;
+    const bool with_bias = bias && n == 0;  // (uniform)
+    f32x4 acc = zero, bacc = zero;
+    for (int w = 0; w < nw; ++w) {
+      const f16x4 ah = *reinterpret_cast<const f16x4*>(pa + 16 * w), al = *reinterpret_cast<const f16x4*>(pa + 16 * us + 16 * w);
+      const f16x4 bh = *reinterpret_cast<const f16x4*>(pb + 16 * w), bl = *reinterpret_cast<const f16x4*>(pb + 16 * us + 16 * w);
+      const f32x4 main = mfma16(ah, bh, zero);
+      f32x4 corr = mfma16(ah, bl, zero);
+      corr = mfma16(al, bh, corr);
+      acc += (corr * kSplitInvScale + main) * (sa[w] * sb[w]);
+      if (with_bias) {
+        const f32x4 bm = mfma16(ah, ones, zero), bc = mfma16(al, ones, zero);
+        bacc += (bc * kSplitInvScale + bm) * sa[w];
+      }
+    }
+    // lane (j, q) register r = dW[delta unit 4 q + r of tile m][input unit j of tile n]
+    const int k = 16 * (n0 + n) + i;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int ow = at.w(m, 4 * q + r, k);
+      if (ow >= 0) atomicAdd(g + ow, acc[r] * out_scale);
+      if (with_bias && i == 0) {
+        const int ob = at.b(m, 4 * q + r);
+        if (ob >= 0) atomicAdd(g + ob, bacc[r] * out_scale);
+      }
+    }
+    n += nw;
+  }
+}
+
 // W^T of a dense Linear W (n_out x n_in) as A blocks: block row i = INPUT unit 16 mi + i, K index = OUTPUT unit.
 // Walked [K-step over outputs][input tile] from K-step ks0: digits (mi, ks - ks0)
 struct DenseTKMajor {
@@ -333,6 +385,30 @@ __device__ __forceinline__ void split_rows(const f32x4 (&v)[MT_MAX], Hidden<MT_M
 #pragma unroll
     for (int r = 0; r < 4; ++r) fm = __builtin_fmaxf(fm, finite_abs(v[m][r]));
   const int e = down_exponent(max_over_q(fm), 13);
+  const float down = pow2f(-e);
+  h.up[0] = pow2f(e);
+  float unused = 0.f;
+#pragma unroll
+  for (int m = 0; m < MT_MAX; ++m) split_tile(v[m] * down, h.hi[0][m], h.lo[0][m], unused);
+}
+
+// the signed e that brings v 2^-e into [2^12, 2^13) (0 for v = 0 or a non-finite v: finite_abs) -- a row scaled this way is
+// split the same whatever power of two its cotangents were multiplied by on the way in
+__device__ __forceinline__ int both_exponent(float fm) {
+  const int e = (int)((__builtin_bit_cast(uint32_t, fm) >> 23) & 0xffu) - 127 - 12;
+  return fm > 0.f ? (e < -100 ? -100 : e) : 0;
+}
+// fp32 tiles -> split tiles with the row's power-of-two scale, UP as well as down: the row's largest entry goes to
+// [2^12, 2^13) (split_rows above only scales down; a one-hot cotangent of a mean loss is ~1/rows and would sit in
+// f16's subnormals).  A row of zeros or non-finite values keeps scale 1.
+template <int MT_MAX>
+__device__ __forceinline__ void split_rows_both(const f32x4 (&v)[MT_MAX], Hidden<MT_MAX, 1>& h) {
+  float fm = 0.f;
+#pragma unroll
+  for (int m = 0; m < MT_MAX; ++m)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) fm = __builtin_fmaxf(fm, finite_abs(v[m][r]));
+  const int e = both_exponent(max_over_q(fm));
   const float down = pow2f(-e);
   h.up[0] = pow2f(e);
   float unused = 0.f;

@@ -1478,7 +1478,8 @@ class NSF_CL(_TwoWayFlow):
 
 
 class _NsfArFn(torch.autograd.Function):
-    """NSF_AR with gradients (mnf_nsf_ar_bwd: recompute, then reverse mode through splines and conditioners)."""
+    """NSF_AR with gradients (recompute, then reverse mode through splines and conditioners: mnf_nsf_ar_bwd, or -- the
+    one-pass direction where NSF_AR._rt_bwd says so, opt-in -- mnf_nsf_ar_bwd_rt on the matrix cores)."""
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, inverse):
@@ -1498,8 +1499,24 @@ class _NsfArFn(torch.autograd.Function):
         gl = None if grad_ld is None else grad_ld.contiguous()
         grad_x = torch.empty_like(x)
         grad_flat = torch.zeros_like(flat)
-        _lib.check("mnf_nsf_ar_bwd", _lib.load().mnf_nsf_ar_bwd(
-            x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), x.shape[0],
+        lib, rows = _lib.load(), x.shape[0]
+        if ctx.inverse and m._rt_bwd(rows):
+            # the one-pass direction on the matrix cores; under MNF_DETERMINISTIC=1 its fixed-order form
+            rt_args = (x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), rows,
+                       m.dim, m.K, float(m.B), len(m.h_sizes), m._hid)
+            rc = _lib.MNF_ERR_UNSUPPORTED
+            if _lib.deterministic():
+                n_ws = lib.mnf_nsf_ar_bwd_rt_det_workspace(rows, m.dim, m.K, len(m.h_sizes), m._hid)
+                if n_ws > 0:
+                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
+                    rc = lib.mnf_nsf_ar_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
+            else:
+                rc = lib.mnf_nsf_ar_bwd_rt(*rt_args, _stream())
+            if rc != _lib.MNF_ERR_UNSUPPORTED:
+                _lib.check("mnf_nsf_ar_bwd_rt", rc)
+                return grad_x, grad_flat, None, None
+        _lib.check("mnf_nsf_ar_bwd", lib.mnf_nsf_ar_bwd(
+            x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), rows,
             m.dim, m.K, float(m.B), int(ctx.inverse), len(m.h_sizes), m._hid, _stream()))
         _lib.note_atomic_sums("NSF_AR.backward", f"dim={m.dim}, K={m.K}, hidden={m.h_sizes}")
         return grad_x, grad_flat, None, None
@@ -1513,7 +1530,10 @@ class NSF_AR(_TwoWayFlow):
     ``mnf_nsf_ar`` launch per direction on the spline device function NSF_CL uses.  The one-pass direction
     (``inverse``: x -> z, what ``log_prob`` and training run through) has a matrix-core forward kernel too
     (``mnf_nsf_ar_rt``, family ``nsf_ar_rt``: four elements' nets side by side per 16-row tile): ``_rt`` sends a call there
-    -- ``_dispatch.NSF_AR_RT_MIN_ROWS``, opt-in as shipped; its gradients stay on ``mnf_nsf_ar_bwd``."""
+    -- ``_dispatch.NSF_AR_RT_MIN_ROWS``, opt-in as shipped; its gradients stay on ``mnf_nsf_ar_bwd`` unless ``_rt_bwd``
+    sends them to ``mnf_nsf_ar_bwd_rt`` (family ``nsf_ar_bwd_rt``, K = 5 or 8; opt-in,
+    ``_dispatch.NSF_AR_BWD_RT_MIN_ROWS``; under ``MNF_DETERMINISTIC=1`` its fixed-order form, so that NSF_AR's parameter
+    gradients repeat bit for bit there).  ``NSF_AR.forward``'s gradients stay on ``mnf_nsf_ar_bwd``."""
 
     def __init__(self, dim: int, K: int = 5, B: float = 3, n_h: int = 8, net_class=MLP) -> None:
         super().__init__()
@@ -1544,6 +1564,18 @@ class NSF_AR(_TwoWayFlow):
         if force != 2 and (_dispatch.NSF_AR_RT_MIN_ROWS is None or rows < _dispatch.NSF_AR_RT_MIN_ROWS):
             return False
         return bool(_lib.load().mnf_nsf_ar_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+
+    def _rt_bwd(self, rows: int) -> bool:
+        """Do the gradients of a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_bwd_rt?  Opt-in, as
+        MAF._rt_seq_bwd: only with _dispatch.NSF_AR_BWD_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not
+        select it), from that many rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1
+        vetoes), never under an fp32 request, and where the library has the shape."""
+        floor = _dispatch.NSF_AR_BWD_RT_MIN_ROWS
+        if floor is None or rows < floor:
+            return False
+        if self._fp32_request() or not _dispatch.wants_rt(rows, int(self.force_generic), False):
+            return False
+        return bool(_lib.load().mnf_nsf_ar_bwd_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
 
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, inverse: bool) -> None:
         """One forward launch: mnf_nsf_ar_rt where `inverse` and _rt says so, else mnf_nsf_ar (an UNSUPPORTED answer of
