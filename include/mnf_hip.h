@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 25
+#define MNF_ABI_VERSION 26
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -439,6 +439,26 @@ int mnf_nsf_ar_bwd_rt_det(const float* x, const float* grad_y, const float* grad
                           const float* flat, int64_t rows, int dim, int K, float tail_bound, int n_hidden,
                           const int* hidden_host, float* workspace, int64_t workspace_floats, void* stream);
 int64_t mnf_nsf_ar_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
+/* The ELEMENT-BY-ELEMENT direction (mnf_nsf_ar's inverse = 0: NSF_AR.forward, z -> x, spline_flow.py:199-216 -- what sampling
+ * runs through, and the density pass of an NSF_AR used the IAF way round) on the f16 matrix pipe (mnf_nsf_ar_seq_rt.hip, kernel
+ * family nsf_ar_seq_rt): x_e, ld_e = RQS_inverse(z_e; net_e(y[:, :e])) of the already decoded output, element
+ * 0 from init_param, log_det = sum_e ld_e.  A wave owns 32 rows and a workgroup's waves walk the elements together: net e (one
+ * unit tile: its widths are at most 16) is staged from `flat` in mnf_nsf_ar's layout (no operand image) as one chunk of LDS,
+ * one barrier per element; the decoded values stay in a per-wave LDS slab, y is written and never read.  Same flat /
+ * tail_bound / log_det conventions as mnf_nsf_ar (here x is z and y is x).  Shapes (mnf_nsf_ar_seq_rt_supported, host only,
+ * the launcher's own plan): 2 <= dim <= 128 (the slab), K = 5 or 8 (the kernel's compile-time list), 1 .. 4 hidden layers of
+ * widths 4 .. 16, flat below 2^31 floats.  MNF_ERR_INVALID_ARG (before any launch): a NULL x / y / flat, x == y, rows < 0,
+ * dim < 1, K < 1, tail_bound <= 0, a NULL or non-positive hidden.  rows == 0: MNF_OK, nothing is launched, no device needed.
+ * A shape outside the plan: MNF_ERR_UNSUPPORTED (the caller runs mnf_nsf_ar).  log_det may be NULL.  A row holding a NaN in
+ * x[:, i]: y[:, :i] as without it, y[:, i:] NaN (the later nets read it), the other rows untouched.  Gradients of this
+ * direction: mnf_nsf_ar_bwd (it recomputes from x). */
+int mnf_nsf_ar_seq_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);
+/* Workgroups of the mnf_nsf_ar_seq_rt launch of `rows` rows (a persistent grid: workgroup b takes the blocks of 32 x waves rows
+ * b, b + grid, ...; 8 / 4 / 2 / 1 waves, as many as the slabs leave room for); 0: nothing to launch, a shape outside the plan,
+ * or no gfx950 device visible. */
+int64_t mnf_nsf_ar_seq_rt_grid(int64_t rows, int dim, int K, int n_hidden, const int* hidden_host);
+int mnf_nsf_ar_seq_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim, int K,
+                      float tail_bound, int n_hidden, const int* hidden_host, void* stream);
 
 /* ------------------------------------------------------------------ Glow: the d x d parameter preparation
  * torch_mnf/flows/glow.py:20-37.  out = W = P (tril(L,-1) + I) (triu(U,1) + diag(S)) (inverse = 0) or its inverse
@@ -916,7 +936,8 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  *   mnf_maf_bwd_rt_supported          1 .. 4 hidden layers of widths 4 .. 64, any dim
  *   mnf_maf_seq_rt_supported          (declared with mnf_maf_seq_rt) mnf_maf_rt's shapes whose net stays resident in LDS
  *   mnf_nsf_ar_rt_supported           (declared with mnf_nsf_ar_rt) K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 16, dim >= 2
- *   mnf_nsf_ar_bwd_rt_supported       (declared with mnf_nsf_ar_bwd_rt) mnf_nsf_ar_rt's shapes with K = 5 or 8 */
+ *   mnf_nsf_ar_bwd_rt_supported       (declared with mnf_nsf_ar_bwd_rt) mnf_nsf_ar_rt's shapes with K = 5 or 8
+ *   mnf_nsf_ar_seq_rt_supported       (declared with mnf_nsf_ar_seq_rt) mnf_nsf_ar_rt's shapes with K = 5 or 8 and dim <= 128 */
 int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
 int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden_host);

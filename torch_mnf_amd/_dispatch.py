@@ -57,7 +57,9 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything                                          | nsf_ar_generic (VALU)          |
 | NSF_AR.inverse bwd       | >= NSF_AR_BWD_RT_MIN_ROWS (opt-in: None) | nsf_ar_rt's shapes with K = 5 or 8      | nsf_ar_bwd_rt                  |
 |                          | else            | anything                                          | nsf_ar_bwd_generic (VALU, atomics) |
-| NSF_AR.forward fwd / bwd | any             | anything (element by element)                     | nsf_ar(_bwd)_generic (VALU)    |
+| NSF_AR.forward fwd       | >= NSF_AR_SEQ_RT_MIN_ROWS (opt-in: None) | 2 <= d <= 128, K = 5 or 8, 1..4 hidden layers of widths 4..16 | nsf_ar_seq_rt |
+|                          | else            | anything (element by element)                     | nsf_ar_generic (VALU)          |
+| NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -201,6 +203,26 @@ NSF_AR_RT_MIN_ROWS = None
 # edit the pinned test would make the default.
 NSF_AR_BWD_RT_MIN_ROWS = None
 
+# NSF_AR, the element-by-element direction (NSF_AR.forward: z -> x, what model.sample() of a model holding an NSF_AR runs
+# through, and the density pass of an NSF_AR used the IAF way round) on the matrix-core kernel nsf_ar_seq_rt
+# (csrc/mnf_nsf_ar_seq_rt.hip; flows.NSF_AR._rt_seq), forward launches only: OPT-IN, with
+# NSF_AR_BWD_RT_MIN_ROWS' semantics.  None: every call stays on nsf_ar_generic, force_generic = 2 included (existing tests pin
+# that kernel for layer.forward under force_generic = 2 and at 4,099 rows); a number sends a call there from that many rows on
+# where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless force_generic = 2 lifts that floor, never with
+# force_generic = 1 or under an fp32 request -- and where mnf_nsf_ar_seq_rt_supported has the shape (dim 2..128, K = 5 or 8,
+# 1..4 hidden layers of widths 4..16).  Its gradients stay on nsf_ar_bwd_generic.
+# Measured (tools/time_nsf_ar_seq_rt.py, profiles/r19/nsf_ar_seq_rt_ab.txt: NSF_AR.forward through the layer under no_grad,
+# nsf_ar_seq_rt against nsf_ar_generic, median of 15 alternating calls, ns per row, at 2,048 / 8,192 / 65,536 / 262,144 rows):
+#   (2, 8, 16)   13.5 against 22.8 | 3.28 / 5.60 | 0.422 / 0.851 | 0.166 / 0.620
+#   (6, 5, 8)    28.2 / 44.0       | 6.97 / 10.9 | 0.898 / 1.76  | 0.442 / 1.27
+#   (16, 8, 8)   66.9 / 119        | 16.6 / 30.9 | 2.15 / 5.30   | 1.18 / 4.54
+#   (64, 5, 8)   249 / 439         | 62.3 / 113  | 8.56 / 33.7   | 5.76 / 31.9
+#   (64, 8, 16)  264 / 541         | 65.9 / 145  | 9.12 / 58.8   | 6.29 / 57.0
+# The kernel wins all twenty cells, each by more than the min-max spread of that cell's nsf_ar_generic timings, the narrowest
+# being (6, 5, 8) at 2,048 rows (1.56 x), the widest (64, 8, 16) at 262,144 (9.06 x).  The smallest row count from which it wins
+# every cell is 2,048 = RT_MIN_ROWS: the value a follow-up that may edit the pinned tests would make the default.
+NSF_AR_SEQ_RT_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -246,16 +268,22 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
-    "nsf" | "rnvp" | "glow" | "maf" | "maf_seq" | "nsf_ar", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
+    "nsf" | "rnvp" | "glow" | "maf" | "maf_seq" | "nsf_ar" | "nsf_ar_seq", direction "fwd" | "bwd", hidden = the conditioner's hidden widths (NSF_CL: (n_h,) * 3;
     Glow: (); Glow "bwd" is the weight gradient's tier -- grad_x has the forward pass's; "maf": the one-pass direction of
     MAF / IAF, hidden = MADE's hidden sizes; "maf_seq": their element-by-element direction, whose "bwd" is "valu"
     unless MAF_SEQ_BWD_RT_MIN_ROWS is set; "nsf_ar": NSF_AR with K and hidden = its nets' hidden widths -- "fwd" is the
     one-pass direction NSF_AR.inverse, "valu" unless NSF_AR_RT_MIN_ROWS is set; "bwd" is its gradient pass, "valu" unless
-    NSF_AR_BWD_RT_MIN_ROWS is set)."""
+    NSF_AR_BWD_RT_MIN_ROWS is set; "nsf_ar_seq": NSF_AR's element-by-element direction NSF_AR.forward -- "fwd" is "valu"
+    unless NSF_AR_SEQ_RT_MIN_ROWS is set, "bwd" is always "valu")."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
+    if kind == "nsf_ar_seq":  # the element-by-element direction: a matrix-core forward kernel, opt-in; gradients on the VALU kernel
+        floor = NSF_AR_SEQ_RT_MIN_ROWS
+        if direction != "fwd" or floor is None or rows < floor or not wants_rt(rows):
+            return "valu"
+        return "rt" if lib.mnf_nsf_ar_seq_rt_supported(dim, K, n, hid) else "valu"
     if kind == "nsf_ar":  # the one-pass direction's kernels are opt-in, the forward and the gradient one each by its own constant
         floor = NSF_AR_RT_MIN_ROWS if direction == "fwd" else NSF_AR_BWD_RT_MIN_ROWS
         if floor is None or rows < floor or not wants_rt(rows):

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 25  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 26  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -240,6 +240,10 @@ SIGNATURES = {
     "mnf_nsf_ar_bwd_rt_det": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float,
                                       c_int, _intp, c_void_p, c_int64, c_void_p]),
     "mnf_nsf_ar_bwd_rt_det_workspace": (c_int64, [c_int64, c_int, c_int, c_int, _intp]),
+    "mnf_nsf_ar_seq_rt_supported": (c_int, [c_int, c_int, c_int, _intp]),
+    "mnf_nsf_ar_seq_rt_grid": (c_int64, [c_int64, c_int, c_int, c_int, _intp]),
+    "mnf_nsf_ar_seq_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_float, c_int, _intp,
+                          c_void_p]),
     "mnf_maf_seq_rt_supported": (c_int, [c_int, c_int, _intp]),
     "mnf_maf_seq_rt_grid": (c_int64, [c_int64, c_int, c_int, _intp]),
     "mnf_maf_seq_rt": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, _intp,

@@ -1533,7 +1533,10 @@ class NSF_AR(_TwoWayFlow):
     -- ``_dispatch.NSF_AR_RT_MIN_ROWS``, opt-in as shipped; its gradients stay on ``mnf_nsf_ar_bwd`` unless ``_rt_bwd``
     sends them to ``mnf_nsf_ar_bwd_rt`` (family ``nsf_ar_bwd_rt``, K = 5 or 8; opt-in,
     ``_dispatch.NSF_AR_BWD_RT_MIN_ROWS``; under ``MNF_DETERMINISTIC=1`` its fixed-order form, so that NSF_AR's parameter
-    gradients repeat bit for bit there).  ``NSF_AR.forward``'s gradients stay on ``mnf_nsf_ar_bwd``."""
+    gradients repeat bit for bit there).  The element-by-element direction (``forward``: z -> x, what sampling runs
+    through) has a matrix-core forward kernel as well (``mnf_nsf_ar_seq_rt``, family ``nsf_ar_seq_rt``: a wave owns 32
+    rows, one net per step, K = 5 or 8, dim <= 128): ``_rt_seq`` sends a call there -- ``_dispatch.NSF_AR_SEQ_RT_MIN_ROWS``,
+    opt-in as shipped.  ``NSF_AR.forward``'s gradients stay on ``mnf_nsf_ar_bwd``."""
 
     def __init__(self, dim: int, K: int = 5, B: float = 3, n_h: int = 8, net_class=MLP) -> None:
         super().__init__()
@@ -1577,10 +1580,29 @@ class NSF_AR(_TwoWayFlow):
             return False
         return bool(_lib.load().mnf_nsf_ar_bwd_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
 
+    def _rt_seq(self, rows: int) -> bool:
+        """Does an element-by-element call (NSF_AR.forward: sampling) go to the matrix-core kernel nsf_ar_seq_rt?  Opt-in,
+        as _rt_bwd: only with _dispatch.NSF_AR_SEQ_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not
+        select it), from that many rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1
+        vetoes), never under an fp32 request, and where the library has the shape.  Forward launches only: the gradients
+        stay on mnf_nsf_ar_bwd, which recomputes from its input."""
+        floor = _dispatch.NSF_AR_SEQ_RT_MIN_ROWS
+        if floor is None or rows < floor:
+            return False
+        if self._fp32_request() or not _dispatch.wants_rt(rows, int(self.force_generic), False):
+            return False
+        return bool(_lib.load().mnf_nsf_ar_seq_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, inverse: bool) -> None:
-        """One forward launch: mnf_nsf_ar_rt where `inverse` and _rt says so, else mnf_nsf_ar (an UNSUPPORTED answer of
-        the former too)."""
+        """One forward launch: mnf_nsf_ar_rt where `inverse` and _rt says so, mnf_nsf_ar_seq_rt where not `inverse` and
+        _rt_seq says so, else mnf_nsf_ar (an UNSUPPORTED answer of the former two too)."""
         lib, rows = _lib.load(), x.shape[0]
+        if not inverse and self._rt_seq(rows):
+            rc = lib.mnf_nsf_ar_seq_rt(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), rows, self.dim,
+                                       self.K, float(self.B), len(self.h_sizes), self._hid, _stream())
+            if rc != _lib.MNF_ERR_UNSUPPORTED:
+                _lib.check("mnf_nsf_ar_seq_rt", rc)
+                return
         if inverse and self._rt(rows):
             rc = lib.mnf_nsf_ar_rt(x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), rows, self.dim,
                                    self.K, float(self.B), len(self.h_sizes), self._hid, _stream())
