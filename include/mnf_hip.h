@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 26
+#define MNF_ABI_VERSION 27
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -816,6 +816,42 @@ int mnf_affine_half_bwd_rt_stack_det(const float* x, const float* outs, const fl
                                      const float* flats, const float* grad_scale_dev, const int* parity_host, int n_layers,
                                      int64_t rows, int dim, int inverse, int n_hidden, const int* hidden_host, int has_scale,
                                      int has_shift, float* workspace, int64_t workspace_floats, void* stream);
+/* The same gradient launches for conditioners whose WIDEST hidden layer has 65 .. 128 units (the kernel's second size class:
+ * eight 16-unit tiles per hidden vector instead of four): 1 .. 4 hidden layers, narrowest >= 4 units, any even dim, scale
+ * and shift as above.  Entry points of their own, so that every existing query keeps its answers: the shapes of
+ * mnf_affine_half_bwd_rt_wide_supported() and those of mnf_affine_half_bwd_rt_supported() are disjoint, and each entry
+ * answers MNF_ERR_UNSUPPORTED for the other's.  Signatures, arguments, argument checks, sum modes and kernel family
+ * names (ahf_bwd_rt, ahf_bwd_stack_rt) are those of the entries above, name for name.  The weight stream holds 16 or
+ * 24 blocks per buffer (the largest chunk, two output tiles' forward blocks and the turned blocks of their K-step, is 16
+ * at 128 units) and the instantiation is compiled for four waves (302 registers, no spills), so a workgroup owns 16 .. 64
+ * rows, four layers of 128 units 32.  A shape that fits no plan is refused, never launched with a clipped buffer.  torch_mnf_amd takes these entries only with
+ * _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS set (opt-in). */
+int mnf_affine_half_bwd_rt_wide_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift);
+int mnf_affine_half_bwd_rt_wide(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                                float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                                int parity, int inverse, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                                void* stream);
+int64_t mnf_affine_half_bwd_rt_wide_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host, int has_scale,
+                                                  int has_shift);
+int mnf_affine_half_bwd_rt_wide_det(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
+                                    float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim,
+                                    int parity, int inverse, int n_hidden, const int* hidden_host, int has_scale,
+                                    int has_shift, float* workspace, int64_t workspace_floats, void* stream);
+int mnf_affine_half_bwd_rt_wide_stack_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                                                int n_layers);
+int mnf_affine_half_bwd_rt_wide_stack(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
+                                      const float* grad_ld, float* grad_x, float* grad_work, float* grad_flats,
+                                      const float* flats, const float* grad_scale_dev, const int* parity_host, int n_layers,
+                                      int64_t rows, int dim, int inverse, int n_hidden, const int* hidden_host,
+                                      int has_scale, int has_shift, void* stream);
+int64_t mnf_affine_half_bwd_rt_wide_stack_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden_host,
+                                                        int has_scale, int has_shift, int n_layers);
+int mnf_affine_half_bwd_rt_wide_stack_det(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
+                                          const float* grad_ld, float* grad_x, float* grad_work, float* grad_flats,
+                                          const float* flats, const float* grad_scale_dev, const int* parity_host,
+                                          int n_layers, int64_t rows, int dim, int inverse, int n_hidden,
+                                          const int* hidden_host, int has_scale, int has_shift, float* workspace,
+                                          int64_t workspace_floats, void* stream);
 int mnf_nsf_cl_bwd(const float* x, const float* grad_y, const float* grad_ld, float* grad_x,
                    float* grad_flat, const float* flat, int64_t rows, int dim, int K, float tail_bound,
                    int inverse, int n_hidden, const int* hidden_host, void* stream);
@@ -924,7 +960,8 @@ int mnf_rnvp_bwd_rt_det(const float* z, const float* mask, uint64_t seed, const 
  * entries then refuse every shape; their *_bwd_rt_det forms take the same shapes).  The limits:
  *   mnf_affine_half_rt_supported      >= 1 hidden layer, widths 4 .. 256, any even dim
  *   mnf_affine_half_bwd_rt_supported  1 .. 4 hidden layers of widths 4 .. 64, any even dim
- *   mnf_nsf_cl_rt_supported           K = 2 .. 16, >= 1 hidden layer, widths 4 .. 64, any even dim
+ *   mnf_affine_half_bwd_rt_wide_supported  (declared with mnf_affine_half_bwd_rt_wide) the same with the widest at 65 .. 128
+ *   mnf_nsf_cl_rt_supported          K = 2 .. 16, >= 1 hidden layer, widths 4 .. 64, any even dim
  *   mnf_nsf_cl_bwd_rt_supported       K = 2 .. 16, 1 .. 4 hidden layers of widths 4 .. 64, any even dim -- and a weight
  *                                     slot (a slot's output blocks and their turned counterparts) of at most 40 blocks
  *                                     that fits 160 KB of LDS with the rest.  With equal widths n_h: K <= 8 any n_h;

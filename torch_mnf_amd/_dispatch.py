@@ -19,6 +19,7 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | any             | the fp32-MFMA kernel's shapes                     | ahf_bwd_mfma_fp32              |
 |                          | >= RT_MIN_ROWS  | 1..4 hidden layers of widths 4..64, any d         | ahf_bwd_rt                     |
 |                          | >= RT_MIN_ROWS, fuse_rt_training | a run of 2..32 such layers of one shape | ahf_bwd_stack_rt (one launch) |
+|                          | >= AHF_BWD_RT_WIDE_MIN_ROWS (opt-in: None) | 1..4 hidden layers, widest 65..128, any d (runs too) | ahf_bwd_rt / ahf_bwd_stack_rt |
 |                          | else            | anything                                          | ahf_bwd_generic                |
 | NSF_CL fwd               | any             | d % 8 == 0 up to 64, n_h <= 16, K 5/8 (10: d<=32) | nsf_mfma_split                 |
 |                          | >= NSF_PAD_MIN_ROWS | other d <= 64 (zero-padded twin layer)        | nsf_mfma_split                 |
@@ -223,6 +224,27 @@ NSF_AR_BWD_RT_MIN_ROWS = None
 # every cell is 2,048 = RT_MIN_ROWS: the value a follow-up that may edit the pinned tests would make the default.
 NSF_AR_SEQ_RT_MIN_ROWS = None
 
+# AffineHalfFlow gradients for conditioners whose widest hidden layer has 65 .. 128 units (h_sizes = (128, 128, 128), (96,),
+# ...) on the second size class of the matrix-core kernel ahf_bwd_rt (csrc/mnf_ahf_bwd_rt.hip, the mnf_affine_half_bwd_rt_wide*
+# entries; flows._ahf_bwd_rt_wide): OPT-IN, with NSF_AR_BWD_RT_MIN_ROWS' semantics.  None: every call stays on
+# ahf_bwd_generic, force_generic = 2 included (an existing test pins that kernel for h_sizes = (128,) at 4,096 rows); a number
+# sends a call there from that many rows on where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless force_generic = 2
+# lifts that floor, never with force_generic = 1 or under an fp32 request -- and where mnf_affine_half_bwd_rt_wide_supported
+# has the shape.  Under MNF_DETERMINISTIC=1 the route runs mnf_affine_half_bwd_rt_wide_det (no atomic sums); with the owner's
+# fuse_rt_training a run of such layers trains as one node on the wide stack entries.
+# Measured (tools/time_ahf_bwd_rt_wide.py, profiles/r20/ahf_bwd_rt_wide_ab.txt: forward + backward through the layer, forward on
+# ahf_rt both times, this route against ahf_bwd_generic, median of 15 alternating calls, ns per row, at 2,048 / 8,192 / 65,536 /
+# 262,144 rows, the fixed-order form too at 65,536):
+#   (64, (128,))            199 against 220 | 49.7 / 56.8 | 7.87 / 23.6 | 4.24 / 18.7 | fixed order 7.69 / 23.1
+#   (64, (96, 96))          183 / 316       | 45.8 / 80.7 | 10.8 / 50.2 | 7.28 / 42.3 |             11.5 / 50.5
+#   (64, (128, 128, 128))   234 / 492       | 61.6 / 224  | 34.5 / 133  | 31.6 / 131  |             37.8 / 135
+#   (512, (128, 128))       376 / 779       | 104 / 508   | 38.3 / 375  | 34.1 / 365  |             37.9 / 374
+# The route wins all sixteen cells and every fixed-order cell; fifteen by more than the min-max spread of that cell's
+# ahf_bwd_generic timings, (64, (128,)) at 8,192 rows inside it (7.1 ahead, spread 8.1).  The smallest row count from which it
+# wins every cell by more than that spread is 65,536: the value a follow-up that may edit the pinned test would make the
+# default.  No cell is lost at any row count.
+AHF_BWD_RT_WIDE_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -274,7 +296,8 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     unless MAF_SEQ_BWD_RT_MIN_ROWS is set; "nsf_ar": NSF_AR with K and hidden = its nets' hidden widths -- "fwd" is the
     one-pass direction NSF_AR.inverse, "valu" unless NSF_AR_RT_MIN_ROWS is set; "bwd" is its gradient pass, "valu" unless
     NSF_AR_BWD_RT_MIN_ROWS is set; "nsf_ar_seq": NSF_AR's element-by-element direction NSF_AR.forward -- "fwd" is "valu"
-    unless NSF_AR_SEQ_RT_MIN_ROWS is set, "bwd" is always "valu")."""
+    unless NSF_AR_SEQ_RT_MIN_ROWS is set, "bwd" is always "valu"; "ahf" "bwd" with the widest hidden layer at 65 .. 128
+    units is "valu" unless AHF_BWD_RT_WIDE_MIN_ROWS is set)."""
     from . import _lib
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
@@ -326,6 +349,8 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     if kind == "ahf":
         query = lib.mnf_affine_half_rt_supported if fwd else lib.mnf_affine_half_bwd_rt_supported
         rt = query(dim, n, hid, int(scale), int(shift))
+        if not rt and not fwd and AHF_BWD_RT_WIDE_MIN_ROWS is not None and rows >= AHF_BWD_RT_WIDE_MIN_ROWS:
+            rt = lib.mnf_affine_half_bwd_rt_wide_supported(dim, n, hid, int(scale), int(shift))  # (opt-in: widest 65 .. 128)
     elif kind == "nsf":
         rt = (lib.mnf_nsf_cl_rt_supported if fwd else lib.mnf_nsf_cl_bwd_rt_supported)(dim, K, n, hid)
     else:

@@ -2,7 +2,8 @@
 // reference trains through these layers: tests/test_flows.py:14-31) for ANY conditioner shape on the f16 matrix pipe:
 // run-time layer count and widths (mnf_rt.h, mnf_rt_bwd.h), weights read from the plain `flat` parameter vector.  Takes
 // the calls the per-shape gradient kernels (mnf_ahf_bwd_split.hip, mnf_ahf_bwd_mfma.hip: three hidden layers of at most
-// 32 units) have no instantiation for: 1 .. 4 hidden layers of widths 4 .. 64, any even dim.
+// 32 units) have no instantiation for: 1 .. 4 hidden layers of widths 4 .. 64, any even dim (MT_MAX = 4: four 16-unit tiles
+// per hidden vector), and -- the *_wide entry points -- the same with the widest layer at 65 .. 128 units (MT_MAX = 8).
 //
 // A workgroup owns a block of 16 NW rows, a wave one tile of it.  Per net (s, then t): the forward recompute keeps every
 // hidden vector (turned, in the LDS exchange area) and the row scales; the output layer is walked two 16-column tiles at
@@ -66,8 +67,18 @@ struct AhfBwdRtLayer {
 
 constexpr float kLog2eB = 1.4426950408889634f;
 
+// Threads the wide instantiation is compiled for; its plan takes at most that many waves.  256 (shipped): one wave per
+// SIMD, 302 registers, no spills, at most 64 rows per workgroup; 512: two waves per SIMD at 256 registers each, 44 of them
+// spilled (180 bytes of scratch per lane), up to 128 rows.  Measured (tools/time_ahf_bwd_rt_wide.py --lib, profiles/r20/):
+// 256 is 5-19 % faster at h_sizes = (128, 128, 128) with the builds timed in either order; the other shapes are level to
+// within what the order of the two builds in a run moves them by.
+#ifndef MNF_AHF_BWD_RT_WIDE_THREADS
+#define MNF_AHF_BWD_RT_WIDE_THREADS 256
+#endif
+static_assert(MNF_AHF_BWD_RT_WIDE_THREADS == 512 || MNF_AHF_BWD_RT_WIDE_THREADS == 256, "8 or 4 waves");
+
 template <int MT_MAX>
-__global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
+__global__ void __launch_bounds__(MT_MAX > 4 ? MNF_AHF_BWD_RT_WIDE_THREADS : 512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
   using namespace rt;
   const bool VEC = a.vec != 0;  // (uniform) rows are 16-byte aligned: dwordx4 row accesses
   extern __shared__ __attribute__((aligned(16))) uint32_t rt_lds[];
@@ -200,7 +211,10 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
                 if (is_s) g = a.inverse ? -gy1[e4] * y1[e4] - gl : gy1[e4] * ex * x1[e4] + gl;
                 else if (after_s) g = a.inverse ? -gxs[e4] : gy1[e4];
                 else g = a.inverse ? -gy1[e4] * ex : gy1[e4];  // (no scale net: ex = 1)
-                g2[ml][e4] = col + e4 < H ? g * gs * rowmask : 0.f;
+                // (wide: a select -- 0 * NaN from a clamped read-back would poison a whole dW block; the narrow
+                //  instantiation keeps the product it shipped with, bit for bit and instruction for instruction)
+                if constexpr (MT_MAX > 4) g2[ml][e4] = col + e4 < H && live ? g * gs : 0.f;
+                else g2[ml][e4] = col + e4 < H ? g * gs * rowmask : 0.f;
               }
               if (pass == 0) store4(gxrow + act_off, col, H, VEC, live, gx1);
             }
@@ -256,9 +270,10 @@ __global__ void __launch_bounds__(512) ahf_bwd_rt_kernel(AhfBwdRtArgs a) {
   }
 }
 
-// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.
-static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, AhfBwdRtArgs& a,
-                            RtPlan& p) {
+// The launch of a shape, or false: the VALU kernel takes it.  Fills the kernel arguments' shape part.  wide: the shapes
+// whose widest hidden layer has 65 .. 128 units (the MT_MAX = 8 instantiation); else those up to 64 (MT_MAX = 4).
+static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, bool wide,
+                            AhfBwdRtArgs& a, RtPlan& p) {
   if (dim < 2 || (dim & 1) || n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || !hidden_ok(n_hidden, hidden) ||
       (!has_scale && !has_shift))
     return false;
@@ -267,7 +282,7 @@ static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_sc
   sizes[0] = H;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   sizes[n_hidden + 1] = H;
-  if (w.min < 4 || w.max > 64) return false;
+  if (w.min < 4 || w.max > (wide ? 128 : 64) || (wide && w.max <= 64)) return false;
   int64_t off = 0;
   if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
   if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
@@ -275,8 +290,8 @@ static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_sc
   if (!has_shift) a.t_net = a.s_net;
   if (off >= (1ll << 31)) return false;
   a.n_params = (int)off;
-  p.mt_max = 4;
-  a.bt = 8;
+  p.mt_max = wide ? 8 : 4;
+  a.bt = 8;  // (a layer's bias tiles: at most 8 at 128 units)
   a.bias_words = 2 * a.bt * 16;
   a.ht_tiles = w.tiles;
   a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
@@ -284,9 +299,12 @@ static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_sc
   // The LDS plan.  Rows per workgroup first (16 per wave, any wave count: the per-row-block cost is what this kernel is
   // bound by), then the roomier of two weight-stream sizes (12 blocks per buffer: fewer chunks; 8: the largest chunk
   // there is -- two output tiles' forward blocks and the transposed blocks of their K-step at 64 hidden units), then as
-  // many first-layer input tiles per chunk as fit (the output-layer chunks need two).
-  for (p.nw = 8; p.nw >= 1; --p.nw) {
-    for (int cb = 12; cb >= 8; cb -= 4) {
+  // many first-layer input tiles per chunk as fit (the output-layer chunks need two).  Wide: that largest chunk is 2 x 4 +
+  // 8 = 16 blocks at 128 hidden units (and a K-step of a 128-unit layer 8), so 24 or 16 blocks per buffer; four layers
+  // of 128 units are 32 exchange tiles, which leave room for 32 rows (nw = 2) beside the 64 KB of weight stream.
+  const int cb_lo = wide ? 16 : 8, cb_step = wide ? 8 : 4;
+  for (p.nw = wide ? MNF_AHF_BWD_RT_WIDE_THREADS / 64 : 8; p.nw >= 1; --p.nw) {
+    for (int cb = cb_lo + cb_step; cb >= cb_lo; cb -= cb_step) {
       int ci = cb / KS1;
       ci = ci > p.mt_max ? p.mt_max : ci < 2 ? 2 : ci;
       for (int ct = ci; ct >= 2; ct = ct > 2 ? 2 : 0) {
@@ -311,7 +329,15 @@ using namespace mnf;
 extern "C" int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
   AhfBwdRtArgs a;
   RtPlan p;
-  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p) ? 1 : 0;
+  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, false, a, p) ? 1 : 0;
+}
+
+// ... and the shapes of the wide instantiation: 1 exactly where the widest hidden layer has 65 .. 128 units and a plan
+// exists -- never where the query above answers 1
+extern "C" int mnf_affine_half_bwd_rt_wide_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
+  AhfBwdRtArgs a;
+  RtPlan p;
+  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
 }
 
 // Which runs go out as one launch: 1 .. 32 layers of a shape the kernel has (every shape class of the plan: the layer
@@ -320,39 +346,60 @@ extern "C" int mnf_affine_half_bwd_rt_stack_supported(int dim, int n_hidden, con
                                                       int n_layers) {
   AhfBwdRtArgs a;
   RtPlan p;
-  return n_layers >= 1 && n_layers <= 32 && ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p) ? 1 : 0;
+  return n_layers >= 1 && n_layers <= 32 && ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, false, a, p) ? 1 : 0;
 }
 
-static DeviceMemo ahf_bwd_rt_attr;
+extern "C" int mnf_affine_half_bwd_rt_wide_stack_supported(int dim, int n_hidden, const int* hidden, int has_scale,
+                                                           int has_shift, int n_layers) {
+  AhfBwdRtArgs a;
+  RtPlan p;
+  return n_layers >= 1 && n_layers <= 32 && ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+}
+
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*ahf_bwd_rt_kernel_of(const RtPlan& p))(AhfBwdRtArgs) {
+  static DeviceMemo attr;
+  allow_big_lds(attr, ahf_bwd_rt_kernel<4>, ahf_bwd_rt_kernel<8>);
+  return p.mt_max == 4 ? ahf_bwd_rt_kernel<4> : ahf_bwd_rt_kernel<8>;
+}
 
 static int64_t ahf_bwd_rt_workspace(int64_t rows, int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
-                                    int n_layers) {
+                                    int n_layers, bool wide) {
   AhfBwdRtArgs a;
   RtPlan p;
   if (rows < 1 || rows * dim >= (1ll << 40) || n_layers < 1 || n_layers > 32 ||
-      !ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p))
+      !ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, wide, a, p))
     return 0;
   if (!gfx950_visible()) return 0;
-  allow_big_lds(ahf_bwd_rt_attr, ahf_bwd_rt_kernel<4>);
-  return rt_det_workspace(ahf_bwd_rt_kernel<4>, p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params);
+  return rt_det_workspace(ahf_bwd_rt_kernel_of(p), p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params);
 }
 
 extern "C" int64_t mnf_affine_half_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden, int has_scale,
                                                         int has_shift) {
-  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, 1);
+  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, 1, false);
+}
+
+extern "C" int64_t mnf_affine_half_bwd_rt_wide_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden,
+                                                             int has_scale, int has_shift) {
+  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, 1, true);
 }
 
 extern "C" int64_t mnf_affine_half_bwd_rt_stack_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden,
                                                               int has_scale, int has_shift, int n_layers) {
-  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, n_layers);
+  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, n_layers, false);
+}
+
+extern "C" int64_t mnf_affine_half_bwd_rt_wide_stack_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden,
+                                                                   int has_scale, int has_shift, int n_layers) {
+  return ahf_bwd_rt_workspace(rows, dim, n_hidden, hidden, has_scale, has_shift, n_layers, true);
 }
 
 // One layer (outs = work = NULL, n_layers = 1, y its output) or a run (y = NULL); lp: grad_ld is d loss / d log p.
-// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd); wide: the *_wide entries' shapes
 static int ahf_bwd_rt_run(const float* x, const float* y, const float* outs, const float* grad_y, const float* grad_ld, int lp,
                           float* grad_x, float* work, float* grad_flat, const float* flat, const float* grad_scale_dev,
                           uint32_t parity_bits, int n_layers, int64_t rows, int dim, int inverse, int n_hidden,
-                          const int* hidden, int has_scale, int has_shift, bool det, float* workspace,
+                          const int* hidden, int has_scale, int has_shift, bool wide, bool det, float* workspace,
                           int64_t workspace_floats, void* stream) {
   if (!x || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
@@ -364,15 +411,14 @@ static int ahf_bwd_rt_run(const float* x, const float* y, const float* outs, con
   AhfBwdRtArgs a;
   memset(&a, 0, sizeof(a));
   RtPlan p;
-  if (!ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, a, p)) return MNF_ERR_UNSUPPORTED;
+  if (!ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, wide, a, p)) return MNF_ERR_UNSUPPORTED;
   a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
   a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity_bits; a.inverse = inverse != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
   a.outs = outs; a.work = work; a.n_layers = n_layers; a.lp = lp;
   // (the planes of outs are rows * dim floats apart: dim % 8 == 0 keeps them aligned with the base)
   a.vec = dim % 8 == 0 && aligned16(x, grad_x, y, grad_y, outs, work);
-  allow_big_lds(ahf_bwd_rt_attr, ahf_bwd_rt_kernel<4>);
-  return launch_rt_bwd(ahf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params, det,
+  return launch_rt_bwd(ahf_bwd_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params, det,
                        workspace, workspace_floats, n_layers > 1 ? "ahf_bwd_stack_rt" : "ahf_bwd_rt", (hipStream_t)stream);
 }
 
@@ -381,7 +427,15 @@ extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const floa
                                       int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                       void* stream) {
   return ahf_bwd_rt_run(x, y, nullptr, grad_y, grad_ld, 0, grad_x, nullptr, grad_flat, flat, grad_scale_dev, parity ? 1u : 0u,
-                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, nullptr, 0, stream);
+                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, false, nullptr, 0, stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt_wide(const float* x, const float* y, const float* grad_y, const float* grad_ld,
+                                           float* grad_x, float* grad_flat, const float* flat, const float* grad_scale_dev,
+                                           int64_t rows, int dim, int parity, int inverse, int n_hidden, const int* hidden,
+                                           int has_scale, int has_shift, void* stream) {
+  return ahf_bwd_rt_run(x, y, nullptr, grad_y, grad_ld, 0, grad_x, nullptr, grad_flat, flat, grad_scale_dev, parity ? 1u : 0u,
+                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, false, nullptr, 0, stream);
 }
 
 extern "C" int mnf_affine_half_bwd_rt_det(const float* x, const float* y, const float* grad_y, const float* grad_ld,
@@ -390,14 +444,25 @@ extern "C" int mnf_affine_half_bwd_rt_det(const float* x, const float* y, const 
                                           int has_scale, int has_shift, float* workspace, int64_t workspace_floats,
                                           void* stream) {
   return ahf_bwd_rt_run(x, y, nullptr, grad_y, grad_ld, 0, grad_x, nullptr, grad_flat, flat, grad_scale_dev, parity ? 1u : 0u,
-                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, workspace, workspace_floats, stream);
+                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, true, workspace, workspace_floats,
+                        stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt_wide_det(const float* x, const float* y, const float* grad_y, const float* grad_ld,
+                                               float* grad_x, float* grad_flat, const float* flat, const float* grad_scale_dev,
+                                               int64_t rows, int dim, int parity, int inverse, int n_hidden,
+                                               const int* hidden, int has_scale, int has_shift, float* workspace,
+                                               int64_t workspace_floats, void* stream) {
+  return ahf_bwd_rt_run(x, y, nullptr, grad_y, grad_ld, 0, grad_x, nullptr, grad_flat, flat, grad_scale_dev, parity ? 1u : 0u,
+                        1, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, true, workspace, workspace_floats,
+                        stream);
 }
 
 // the run's own argument checks (before any launch), then ahf_bwd_rt_run
 static int ahf_bwd_rt_stack(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
                             const float* grad_ld, float* grad_x, float* grad_work, float* grad_flats, const float* flats,
                             const float* grad_scale_dev, const int* parity_host, int n_layers, int64_t rows, int dim,
-                            int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift, bool det,
+                            int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift, bool wide, bool det,
                             float* workspace, int64_t workspace_floats, void* stream) {
   if (!x || !outs || !grad_x || !flats || !grad_scale_dev || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 ||
       (lp_grad && (grad_y_last || grad_ld)) || (n_layers > 1 && !grad_work) || grad_work == grad_x || x == outs ||
@@ -410,7 +475,7 @@ static int ahf_bwd_rt_stack(const float* x, const float* outs, const float* grad
   for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
   return ahf_bwd_rt_run(x, nullptr, outs, grad_y_last, lp_grad ? lp_grad : grad_ld, lp_grad ? 1 : 0, grad_x,
                         n_layers > 1 ? grad_work : nullptr, grad_flats, flats, grad_scale_dev, bits, n_layers, rows, dim,
-                        inverse, n_hidden, hidden, has_scale, has_shift, det, workspace, workspace_floats, stream);
+                        inverse, n_hidden, hidden, has_scale, has_shift, wide, det, workspace, workspace_floats, stream);
 }
 
 extern "C" int mnf_affine_half_bwd_rt_stack(const float* x, const float* outs, const float* grad_y_last, const float* lp_grad,
@@ -419,8 +484,18 @@ extern "C" int mnf_affine_half_bwd_rt_stack(const float* x, const float* outs, c
                                             int n_layers, int64_t rows, int dim, int inverse, int n_hidden, const int* hidden,
                                             int has_scale, int has_shift, void* stream) {
   return ahf_bwd_rt_stack(x, outs, grad_y_last, lp_grad, grad_ld, grad_x, grad_work, grad_flats, flats, grad_scale_dev,
-                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, nullptr, 0,
-                          stream);
+                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, false,
+                          nullptr, 0, stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt_wide_stack(const float* x, const float* outs, const float* grad_y_last,
+                                                 const float* lp_grad, const float* grad_ld, float* grad_x, float* grad_work,
+                                                 float* grad_flats, const float* flats, const float* grad_scale_dev,
+                                                 const int* parity_host, int n_layers, int64_t rows, int dim, int inverse,
+                                                 int n_hidden, const int* hidden, int has_scale, int has_shift, void* stream) {
+  return ahf_bwd_rt_stack(x, outs, grad_y_last, lp_grad, grad_ld, grad_x, grad_work, grad_flats, flats, grad_scale_dev,
+                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, false,
+                          nullptr, 0, stream);
 }
 
 extern "C" int mnf_affine_half_bwd_rt_stack_det(const float* x, const float* outs, const float* grad_y_last,
@@ -430,6 +505,18 @@ extern "C" int mnf_affine_half_bwd_rt_stack_det(const float* x, const float* out
                                                 int n_hidden, const int* hidden, int has_scale, int has_shift,
                                                 float* workspace, int64_t workspace_floats, void* stream) {
   return ahf_bwd_rt_stack(x, outs, grad_y_last, lp_grad, grad_ld, grad_x, grad_work, grad_flats, flats, grad_scale_dev,
-                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, workspace,
-                          workspace_floats, stream);
+                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, false, true,
+                          workspace, workspace_floats, stream);
+}
+
+extern "C" int mnf_affine_half_bwd_rt_wide_stack_det(const float* x, const float* outs, const float* grad_y_last,
+                                                     const float* lp_grad, const float* grad_ld, float* grad_x,
+                                                     float* grad_work, float* grad_flats, const float* flats,
+                                                     const float* grad_scale_dev, const int* parity_host, int n_layers,
+                                                     int64_t rows, int dim, int inverse, int n_hidden, const int* hidden,
+                                                     int has_scale, int has_shift, float* workspace, int64_t workspace_floats,
+                                                     void* stream) {
+  return ahf_bwd_rt_stack(x, outs, grad_y_last, lp_grad, grad_ld, grad_x, grad_work, grad_flats, flats, grad_scale_dev,
+                          parity_host, n_layers, rows, dim, inverse, n_hidden, hidden, has_scale, has_shift, true, true,
+                          workspace, workspace_floats, stream);
 }

@@ -359,6 +359,15 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
                 rc = lib.mnf_affine_half_bwd_rt_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
         else:
             rc = lib.mnf_affine_half_bwd_rt(*args, _stream())
+        if rc == _lib.MNF_ERR_UNSUPPORTED and _ahf_bwd_rt_wide(lib, f, rows):
+            # widest hidden layer 65 .. 128 units: the kernel's second size class (opt-in, the same arguments)
+            if _lib.deterministic():
+                n_ws = lib.mnf_affine_half_bwd_rt_wide_det_workspace(rows, f.dim, *hid, int(f.scale), int(f.shift))
+                if n_ws > 0:
+                    ws = _rt_det_workspace(n_ws, grad_flat_ptr, x_in.device)
+                    rc = lib.mnf_affine_half_bwd_rt_wide_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
+            else:
+                rc = lib.mnf_affine_half_bwd_rt_wide(*args, _stream())
     if rc == _lib.MNF_ERR_UNSUPPORTED:  # no matrix-core gradient kernel for this shape at all
         rc = lib.mnf_affine_half_bwd(
             x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, rows, f.dim,
@@ -370,6 +379,19 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
     if grad_flat_ptr is not None:
         _lib.note_atomic_sums("AffineHalfFlow.backward", shape)
     return True
+
+
+def _ahf_bwd_rt_wide(lib, f, rows: int) -> bool:
+    """Do the gradients of an AffineHalfFlow call whose widest hidden layer has 65 .. 128 units go to the matrix-core kernel's
+    wide entries (mnf_affine_half_bwd_rt_wide*)?  Opt-in, as NSF_AR._rt_bwd: only with _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS set
+    (None: never -- force_generic = 2 alone does not select it), from that many rows on, where _dispatch.wants_rt says so
+    (force_generic = 2 lifts its row floor, 1 vetoes), never under an fp32 request, and where the library has the shape."""
+    floor = _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS
+    if floor is None or rows < floor:
+        return False
+    if f._fp32_request() or not _dispatch.wants_rt(rows, int(f.force_generic), False):
+        return False
+    return bool(lib.mnf_affine_half_bwd_rt_wide_supported(f.dim, len(f.h_sizes), f._hid, int(f.scale), int(f.shift)))
 
 
 class _AffineHalfFn(torch.autograd.Function):
@@ -846,6 +868,9 @@ def _rt_layer_scales(lib, run, x: Tensor, buf: Tensor, flat: Tensor, g_last, gl,
     scales = torch.ones(n, dtype=torch.float32, device=x.device)
     order = list(reversed(run.layers)) if inverse else list(run.layers)
     n_params = flat.numel() // n
+    # (the narrow and the wide entries' shapes are disjoint: a run that got here has one or the other)
+    narrow = lib.mnf_affine_half_bwd_rt_supported(dim, len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift))
+    layer_bwd = lib.mnf_affine_half_bwd_rt_det if narrow else lib.mnf_affine_half_bwd_rt_wide_det
     for li in range(n - 1, -1, -1):
         if g is not None or gls is not None:
             _lib.check("mnf_affine_half_grad_scale", lib.mnf_affine_half_grad_scale(
@@ -854,7 +879,7 @@ def _rt_layer_scales(lib, run, x: Tensor, buf: Tensor, flat: Tensor, g_last, gl,
             break
         f = order[li]
         gx = torch.empty_like(xs)
-        _lib.check("mnf_affine_half_bwd_rt", lib.mnf_affine_half_bwd_rt_det(
+        _lib.check("mnf_affine_half_bwd_rt", layer_bwd(
             outs[li - 1].data_ptr(), outs[li].data_ptr(), _ptr(g), _ptr(gls), gx.data_ptr(), None,
             flat.data_ptr() + 4 * n_params * run.layers.index(f), scales[li:].data_ptr(), sample, dim, int(bool(f.parity)),
             int(inverse), len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), None, 0, _stream()))
@@ -983,8 +1008,15 @@ class _AffineRunFn(torch.autograd.Function):
         gx = torch.empty_like(x)
         one_launch = all(g is None for g in grads[:n - 1])
         n_ws = 0
+        # the run's entries: the wide ones where the widest hidden layer has 65 .. 128 units (rt_train_route let it in)
+        wide = not lib.mnf_affine_half_bwd_rt_stack_supported(f0.dim, *hid, int(f0.scale), int(f0.shift), n)
+        stack_ws, stack_det, stack_bwd = (
+            (lib.mnf_affine_half_bwd_rt_wide_stack_det_workspace, lib.mnf_affine_half_bwd_rt_wide_stack_det,
+             lib.mnf_affine_half_bwd_rt_wide_stack) if wide else
+            (lib.mnf_affine_half_bwd_rt_stack_det_workspace, lib.mnf_affine_half_bwd_rt_stack_det,
+             lib.mnf_affine_half_bwd_rt_stack))
         if one_launch and _lib.deterministic() and grad_flat is not None:
-            n_ws = lib.mnf_affine_half_bwd_rt_stack_det_workspace(rows, f0.dim, *hid, int(f0.scale), int(f0.shift), n)
+            n_ws = stack_ws(rows, f0.dim, *hid, int(f0.scale), int(f0.shift), n)
             one_launch = n_ws > 0  # (no fixed-order launch for the call: the layers one by one, as they do by themselves)
         if one_launch:
             g_last = None if grads[n - 1] is None else grads[n - 1].contiguous()
@@ -997,9 +1029,9 @@ class _AffineRunFn(torch.autograd.Function):
                     int(f0.scale), int(f0.shift))
             if _lib.deterministic():
                 ws = _rt_det_workspace(n_ws, _ptr(grad_flat), dev)
-                rc = lib.mnf_affine_half_bwd_rt_stack_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
+                rc = stack_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
             else:
-                rc = lib.mnf_affine_half_bwd_rt_stack(*args, _stream())
+                rc = stack_bwd(*args, _stream())
             _lib.check("mnf_affine_half_bwd_rt_stack", rc)
             g = gx
         else:
@@ -2469,6 +2501,7 @@ class _AffineRun:
         self._rt_flat: Tensor | None = None
         self._rt_shape_ok = None  # mnf_affine_half_rt_stack_supported, asked once
         self._rt_bwd_ok = None    # mnf_affine_half_bwd_rt_stack_supported, asked once
+        self._rt_bwd_wide_ok = None  # mnf_affine_half_bwd_rt_wide_stack_supported, asked once
         self._rt_now = False      # the call in flight trains on the run-time-shaped route (launch_grad -> _AffineRunFn)
         # the owner's switch (NormalizingFlow / FusedAffineStack .fuse_rt_training), copied here before every pass
         self.fuse_rt_training = False
@@ -2642,11 +2675,18 @@ class _AffineRun:
         kernels -- ``rt_route``'s conditions, and the library has the gradient launch for the run too."""
         if not self.fuse_rt_training or not self.rt_route(rows, device):
             return False
+        f0 = self.layers[0]
         if self._rt_bwd_ok is None:
-            f0 = self.layers[0]
             self._rt_bwd_ok = bool(_lib.load().mnf_affine_half_bwd_rt_stack_supported(
                 f0.dim, len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), len(self.layers)))
-        return self._rt_bwd_ok
+        if self._rt_bwd_ok:
+            return True
+        # widest hidden layer 65 .. 128 units: the wide stack entries, where every layer by itself would take the wide route
+        # (_ahf_bwd_rt_wide: opt-in through _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS, read at every call)
+        if self._rt_bwd_wide_ok is None:
+            self._rt_bwd_wide_ok = bool(_lib.load().mnf_affine_half_bwd_rt_wide_stack_supported(
+                f0.dim, len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift), len(self.layers)))
+        return self._rt_bwd_wide_ok and all(_ahf_bwd_rt_wide(_lib.load(), f, rows) for f in self.layers)
 
     def trainable(self, x) -> bool:
         """Gradients wanted and the whole run can go through one autograd node (stack kernel forward; backward
@@ -2689,7 +2729,7 @@ class _AffineRun:
                 self._lp_unsupported = refused
                 return None
             if self._rt_now:
-                self._rt_bwd_ok = False
+                self._rt_bwd_ok = self._rt_bwd_wide_ok = False
             else:
                 self._unsupported = True
             return None
