@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 27
+#define MNF_ABI_VERSION 28
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -665,6 +665,26 @@ int mnf_mnf_conv_operands_bwd(const float* W_mean, const float* W_log_var, const
                               int accumulate, void* stream);
 int mnf_mnf_noise(const float* mean, const float* var, const float* eps, float* out, int64_t n, void* stream);
 int mnf_mnf_noise_bwd(const float* var, const float* eps, const float* grad_out, float* grad_var, int64_t n, void* stream);
+
+/* ------------------------------------------------ MNFConv2d.forward behind its operands as ONE launch
+ * torch_mnf/layers/mnf_conv.py:67-88 (algorithm 2 of the paper): both convolutions and the noise epilogue on the exact-fp32
+ * matrix instruction, for contiguous NCHW float32 x (batch, n_in, height, width), stride 1, no padding, no dilation, one
+ * group -- all the layer asks for:
+ *   out[n, co, oy, ox] = fma(sqrt(v), eps[n, co, oy, ox], m)
+ *   m = b_mean[co] + sum_k x[n, ci, oy + ky, ox + kx]   * Wz[co, k]       k = (ci, ky, kx)
+ *   v = b_var[co]  + sum_k x[n, ci, oy + ky, ox + kx]^2 * W_var[co, k]
+ * Wz, W_var (n_out, n_in, k, k) and b_var (n_out) are mnf_mnf_conv_operands' outputs; eps, out and var_out are
+ * (batch, n_out, height - k + 1, width - k + 1); var_out may be NULL, else it receives v (the gradient pass needs it).
+ * The sums run in k order, one rounding per term, so a call repeats bit for bit; no atomics, no workspace, no host
+ * synchronisation (capturable in a hipGraph).  Kernel family "mnf_conv_fwd".
+ *   _supported  1 for 1 <= n_out <= 64, 1 <= n_in k^2 <= 4096, height, width >= k >= 1 (and max(n_in, 64) * height * width
+ *               below 2^31: the offsets inside an image are 32-bit), else 0
+ *   the entry   MNF_ERR_INVALID_ARG on a null pointer (var_out excepted) or a non-positive size, MNF_ERR_UNSUPPORTED
+ *               outside _supported or from 2^31 - 256 output pixels (batch * (height - k + 1) * (width - k + 1)) on */
+int mnf_mnf_conv_fwd_supported(int n_in, int n_out, int kernel_size, int height, int width);
+int mnf_mnf_conv_fwd(const float* x, const float* Wz, const float* W_var, const float* b_mean, const float* b_var,
+                     const float* eps, float* out, float* var_out, int64_t batch, int n_in, int height, int width,
+                     int n_out, int kernel_size, void* stream);
 
 /* ------------------------------------------------------------------ gradients (autograd)
  * What torch.autograd.Function.backward needs so the modules train like the reference's

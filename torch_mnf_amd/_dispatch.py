@@ -61,6 +61,8 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | NSF_AR.forward fwd       | >= NSF_AR_SEQ_RT_MIN_ROWS (opt-in: None) | 2 <= d <= 128, K = 5 or 8, 1..4 hidden layers of widths 4..16 | nsf_ar_seq_rt |
 |                          | else            | anything (element by element)                     | nsf_ar_generic (VALU)          |
 | NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
+| MNFConv2d.forward        | MNF_CONV_FUSED (opt-in: False) | n_out <= 64, n_in k^2 <= 4096          | mnf_conv_fwd (one launch behind the operands) |
+|                          | else            | anything                                          | MIOpen convolutions between the library's operand and noise launches |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -244,6 +246,26 @@ NSF_AR_SEQ_RT_MIN_ROWS = None
 # wins every cell by more than that spread is 65,536: the value a follow-up that may edit the pinned test would make the
 # default.  No cell is lost at any row count.
 AHF_BWD_RT_WIDE_MIN_ROWS = None
+
+# MNFConv2d.forward behind sample_z and the operand launch as ONE matrix-core launch (csrc/mnf_mnf_conv_fwd.hip, family
+# mnf_conv_fwd; layers._MnfConvFwdFn): both convolutions on the exact-fp32 matrix instruction with the noise
+# epilogue fused, instead of two MIOpen convolutions, the x * x launch and the noise launch: OPT-IN.  False: forward is the
+# route it has always been, launch for launch; True sends a call there wherever mnf_mnf_conv_fwd_supported has the shape
+# (n_out <= 64, n_in k^2 <= 4096), at any batch size.  Its gradients stay where they are: the noise gradient launch and
+# aten's convolution_backward, twice.
+# Measured (tools/time_mnf_conv_fwd.py, profiles/r21/mnf_conv_fwd_ab.txt: layer.forward, this route against the current one
+# timed twice, median of 15 alternating calls, microseconds per call, at batch 128 / 1,024 / 8,192):
+#   MNFConv2d(1, 20, 5) 28x28   forward, no_grad   154 against 182 / 187 | 196 / 303 / 307 | 729 / 1,573 / 1,581
+#                               forward + backward 572 / 600 / 604       | 917 / 997 / 1,009 | 2,852 / 3,621 / 3,628
+#   MNFConv2d(20, 50, 5) 12x12  forward, no_grad   176.4 / 173.6 / 178.1 | 233 / 286 / 287 | 943 / 1,204 / 1,214
+#                               forward + backward 943 / 1,002 / 1,016   | 1,042 / 1,063 / 1,060 | 4,806 / 5,050 / 5,046
+#   MNFLeNet forward, no_grad   128 rows 506 / 598 / 592 | 4,096 rows 1,252 / 1,830 / 1,830
+# GPU kernels per layer forward 8 against 13.  Eleven of the twelve layer cells and both LeNet lines are won by more than the
+# current route's spread (1.18-2.16 x forward, 1.02-1.27 x forward + backward, where the unchanged gradient convolutions
+# dominate).  Not won: the second convolution's forward at batch 128, which lands between the current route's two medians
+# (level).  The smallest batch from which the route wins every cell by more than that spread is 1,024: the threshold a
+# follow-up would give the switch.
+MNF_CONV_FUSED = False
 
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 

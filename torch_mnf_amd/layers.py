@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from . import _lib
+from . import _dispatch, _lib
 from . import flows as _flows
 from ._lib import MnfHipError
 from .flows import MADE, RNVP, MaskedLinear, NormalizingFlow, _stream, _wants_grad  # noqa: F401 (MADE, MaskedLinear: torch_mnf.layers exports them)
@@ -230,6 +230,61 @@ class _NoiseFn(torch.autograd.Function):
         _lib.check("mnf_mnf_noise_bwd", _lib.load().mnf_mnf_noise_bwd(v.data_ptr(), e.data_ptr(), gc.data_ptr(),
                                                                      gv.data_ptr(), v.numel(), _stream()))
         return gc, gv, None
+
+
+class _MnfConvFwdFn(torch.autograd.Function):
+    """MNFConv2d.forward behind its operands (mnf_conv.py:73-88) as ONE launch, ``mnf_mnf_conv_fwd``: both convolutions on
+    the exact-fp32 matrix instruction and the noise epilogue (_dispatch.MNF_CONV_FUSED).  ``eps`` None: drawn here, before
+    the launch.  Backward has no kernel of its own: the noise gradient launch, then aten's convolution_backward once per
+    convolution -- what the MIOpen route's autograd graph runs too."""
+
+    @staticmethod
+    def forward(ctx, x, Wz, W_var, b_var, b_mean, eps):
+        for name, t in (("x", x), ("Wz", Wz), ("W_var", W_var), ("b_var", b_var), ("b_mean", b_mean)):
+            if not t.is_cuda or t.dtype != torch.float32 or t.device != x.device:
+                raise RuntimeError(f"torch_mnf_amd: mnf_mnf_conv_fwd needs float32 tensors on one GPU, got {name}: "
+                                   f"{t.dtype} on {t.device}; the HIP path has no CPU fallback")
+        xc, wz, wv, bv, bm = (t.detach().contiguous() for t in (x, Wz, W_var, b_var, b_mean))
+        batch, n_in, height, width = xc.shape
+        n_out, k = wz.shape[0], wz.shape[-1]
+        shape = (batch, n_out, height - k + 1, width - k + 1)
+        if eps is None:
+            e = torch.randn(shape, dtype=torch.float32, device=xc.device)
+        else:
+            e = eps.detach().to(xc.device, torch.float32).contiguous()
+            if tuple(e.shape) != shape:
+                raise ValueError(f"eps must be {shape}, got {tuple(e.shape)}")
+        out = torch.empty(shape, dtype=torch.float32, device=xc.device)
+        # (needs_input_grad is the inputs' requires_grad whatever the grad mode, and the mode is always off in here: the
+        # layer detaches x under no_grad, so that a call without a gradient pass neither stores var nor saves tensors)
+        training = any(ctx.needs_input_grad[:4])
+        var = torch.empty_like(out) if training else None  # the gradient pass needs it
+        _lib.check("mnf_mnf_conv_fwd", _lib.load().mnf_mnf_conv_fwd(
+            xc.data_ptr(), wz.data_ptr(), wv.data_ptr(), bm.data_ptr(), bv.data_ptr(), e.data_ptr(), out.data_ptr(),
+            _flows._ptr(var), batch, n_in, height, width, n_out, k, _stream()))
+        if training:
+            ctx.save_for_backward(xc, wz, wv, var, e)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        xc, wz, wv, var, e = ctx.saved_tensors
+        need_x, need_wz, need_wv, need_bv = ctx.needs_input_grad[:4]
+        gc = g.contiguous()
+        conv_bwd = torch.ops.aten.convolution_backward
+        geometry = ([wz.shape[0]], [1, 1], [0, 0], [1, 1], False, [0, 0], 1)  # bias_sizes, stride, padding, dilation, ...
+        gx = g_wz = g_wv = g_bv = None
+        if need_x or need_wz:
+            gx, g_wz, _ = conv_bwd(gc, xc, wz, *geometry, [need_x, need_wz, False])
+        if need_x or need_wv or need_bv:
+            gv = torch.empty_like(var)
+            _lib.check("mnf_mnf_noise_bwd", _lib.load().mnf_mnf_noise_bwd(var.data_ptr(), e.data_ptr(), gc.data_ptr(),
+                                                                         gv.data_ptr(), var.numel(), _stream()))
+            gx2, g_wv, g_bv = conv_bwd(gv, xc * xc, wv, *geometry, [need_x, need_wv, need_bv])
+            if need_x:
+                gx = gx + 2 * xc * gx2  # d (x * x) = 2 x
+        return gx, g_wz, g_wv, g_bv, None, None
 
 
 class _MnfKlFn(torch.autograd.Function):
@@ -605,7 +660,11 @@ class MNFConv2d(nn.Module):
 
     What is on the library's path here is the flow: ``sample_z`` pushes one n_out-vector through ``flow_q`` (RNVP
     layers, HIP kernels) and ``kl_div`` one through ``flow_r``.  The two convolutions are the caller's arithmetic
-     and stay ``F.conv2d`` on device tensors.  Noise can be injected for reproducible runs:
+     and by default stay ``F.conv2d`` on device tensors (MIOpen), between the library's operand
+    and noise launches.  With ``_dispatch.MNF_CONV_FUSED = True`` (opt-in) and n_out <= 64, n_in * kernel_size**2 <= 4096,
+    everything behind the operand launch -- both convolutions and the noise epilogue -- is ONE launch of the library's
+    own (``mnf_mnf_conv_fwd``, exact-fp32 matrix instruction; its gradients: the noise gradient launch and aten's
+    convolution_backward).  Noise can be injected for reproducible runs:
     ``eps_z`` (n_out,), ``masks`` (one (1, n_out) float mask per flow layer), ``eps`` (shape of the output)."""
 
     def __init__(self, n_in: int, n_out: int, kernel_size: int, n_flows_q: int = 2, n_flows_r: int = 2,
@@ -655,9 +714,23 @@ class MNFConv2d(nn.Module):
         # two convolutions are the caller's arithmetic (MIOpen)
         Wz, W_var, b_var = _ConvOperandsFn.apply(self.W_mean, self.W_log_var, self.b_log_var, z, self)
         b_mean = self.b_mean if self.b_mean.device == x.device else self.b_mean.to(x.device)
+        if _dispatch.MNF_CONV_FUSED and self._fused_forward_has(x):  # opt-in: everything below as one launch
+            return _MnfConvFwdFn.apply(x if torch.is_grad_enabled() else x.detach(), Wz, W_var, b_var, b_mean, eps)
         mean = F.conv2d(x, weight=Wz, bias=b_mean)
         var = F.conv2d(x * x, weight=W_var, bias=b_var)
         return _NoiseFn.apply(mean, var, torch.randn_like(var) if eps is None else eps.to(var.device))
+
+    def _fused_forward_has(self, x: Tensor) -> bool:
+        """True where ``mnf_mnf_conv_fwd`` has this input: float32 on the layer's GPU, the library's shape query, and a
+        32-bit output pixel count."""
+        if not x.is_cuda or x.dtype != torch.float32 or x.device != self.W_mean.device:
+            return False  # (forward has refused these already; anything else that asks here gets the shipped route's error)
+        if x.dim() != 4 or x.shape[0] < 1 or x.shape[1] != self.n_in:
+            return False
+        k, (height, width) = self.kernel_size, x.shape[2:]
+        if not _lib.load().mnf_mnf_conv_fwd_supported(self.n_in, self.n_out, k, height, width):
+            return False
+        return x.shape[0] * (height - k + 1) * (width - k + 1) < 2 ** 31 - 256
 
     def kl_div(self, noise: dict | None = None) -> Tensor:
         """(mnf_conv.py:100-133): both flows, then every closed-form term in one launch (``mnf_mnf_kl_fwd``).
