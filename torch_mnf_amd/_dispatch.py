@@ -1,4 +1,6 @@
-"""Which kernel family a layer call takes: every shape / row-count threshold of the Python layer in one place.
+"""Which kernel family a layer call takes: every shape / row-count threshold of the Python layer in one place, and the
+rule that reads them -- the routes the Python layer decides by itself (MAF / IAF, NSF_AR, the wide AffineHalfFlow
+gradients) are the rows of RT_ROUTES, decided by rt_route() alone: the layers' predicates in flows.py and tier() both ask it.
 
 The C library picks among its kernels by SHAPE (a specialised kernel where the shape has one, else the run-time-shaped
 matrix-core kernels of csrc/mnf_rt.h, else the VALU any-shape kernels); what is decided here is by ROW COUNT -- where a
@@ -92,6 +94,7 @@ workgroup, added up in order; same kernel family names, same tiers); the VALU gr
 per layer and shape (_lib.note_atomic_sums).
 layer.force_generic = 1 / 2 forces the VALU / the run-time-shaped kernels (tests, tools/coverage_map.py).
 """
+from dataclasses import dataclass
 
 # The run-time-shaped matrix-core kernels (csrc/mnf_rt.h: any layer count and widths) take a call without a per-shape
 # kernel from this many rows on; below, the VALU any-shape kernels (a workgroup per few rows) have the lower latency.
@@ -159,11 +162,8 @@ MAF_SEQ_RT_MIN_ROWS = 2048
 # MAF / IAF, the gradients of the element-by-element direction (what an IAF is trained through: IAF.inverse is its density
 # pass) on the matrix cores (csrc/mnf_maf_seq_bwd_rt.hip, family maf_seq_bwd_rt; flows.MAF._rt_seq_bwd, DESIGN.md 3.8g: a
 # triangular solve for the total cotangents, then the one-pass direction's weight pass maf_bwd_rt at the decoded output):
-# OPT-IN.  None: every call stays on maf_bwd_generic, force_generic = 2 included (existing tests pin that kernel under
-# force_generic = 2); a number sends a call there from that many rows on where _dispatch.wants_rt says so -- so never below
-# RT_MIN_ROWS unless the layer's force_generic = 2 lifts that floor, never with force_generic = 1 -- and where
-# mnf_maf_seq_bwd_rt_supported has the shape.  Under MNF_DETERMINISTIC=1 the route runs mnf_maf_seq_bwd_rt_det (no atomic
-# sums).  Measured (tools/time_maf_seq_bwd_rt.py, profiles/r16/maf_seq_bwd_rt_ab.txt: forward + backward, this route against
+# OPT-IN (RT_ROUTES "maf_seq_bwd"; existing tests pin maf_bwd_generic under force_generic = 2).  Under MNF_DETERMINISTIC=1
+# the route runs mnf_maf_seq_bwd_rt_det (no atomic sums).  Measured (tools/time_maf_seq_bwd_rt.py, profiles/r16/maf_seq_bwd_rt_ab.txt: forward + backward, this route against
 # maf_bwd_generic, at (dim, hidden) = (2, 24x3), (6, 16x2), (64, 24x3), (64, 64x2) and 2,048 / 8,192 / 65,536 rows, the fixed-order
 # form too at 65,536): the route wins every cell, the narrowest being (2, 24x3) at 2,048 rows, 212 against 288 ns per row;
 # (64, 64x2) at 65,536 rows: 29.3 against 11,990.  The smallest row count from which it wins every cell is 2,048 = RT_MIN_ROWS:
@@ -171,11 +171,9 @@ MAF_SEQ_RT_MIN_ROWS = 2048
 MAF_SEQ_BWD_RT_MIN_ROWS = None
 
 # NSF_AR, the one-pass direction (NSF_AR.inverse: x -> z, what log_prob and training run through) on the matrix-core kernel
-# nsf_ar_rt (csrc/mnf_nsf_ar_rt.hip; flows.NSF_AR._rt), forward launches only: OPT-IN.  None: only a layer's
-# force_generic = 2 reaches the kernel (an existing test runs this direction above RT_MIN_ROWS and pins the VALU kernel); a
-# number sends a call there from that many rows on where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless
-# force_generic = 2 lifts that floor, never with force_generic = 1 or under an fp32 request -- and where
-# mnf_nsf_ar_rt_supported has the shape.  Measured (tools/time_nsf_ar_rt.py, profiles/r17/nsf_ar_rt_ab.txt: NSF_AR.inverse
+# nsf_ar_rt (csrc/mnf_nsf_ar_rt.hip; flows.NSF_AR._rt), forward launches only: None as shipped, so
+# only a layer's force_generic = 2 reaches the kernel (RT_ROUTES "nsf_ar", by name; an existing test runs this direction above
+# RT_MIN_ROWS and pins the VALU kernel).  Measured (tools/time_nsf_ar_rt.py, profiles/r17/nsf_ar_rt_ab.txt: NSF_AR.inverse
 # through the layer, nsf_ar_rt against nsf_ar_generic, at (dim, K, n_h) = (2, 8, 16), (6, 5, 8), (16, 8, 8), (64, 5, 8),
 # (64, 8, 16) and 2,048 / 8,192 / 65,536 / 262,144 rows): the kernel wins all twenty cells, the narrowest being
 # (2, 8, 16) at 2,048 rows, 19.3 against 23.0 ns per row (1.19 x; at 262,144 rows 0.34 against 0.61); (64, 8, 16) at 262,144
@@ -184,12 +182,9 @@ MAF_SEQ_BWD_RT_MIN_ROWS = None
 NSF_AR_RT_MIN_ROWS = None
 
 # NSF_AR, the gradients of the one-pass direction (every Adam step of an NSF_AR density model) on the matrix-core kernel
-# nsf_ar_bwd_rt (csrc/mnf_nsf_ar_bwd_rt.hip; flows.NSF_AR._rt_bwd): OPT-IN, with MAF_SEQ_BWD_RT_MIN_ROWS'
-# semantics.  None: every call stays on nsf_ar_bwd_generic, force_generic = 2 included (an existing test pins that kernel
-# under force_generic = 2); a number sends a call there from that many rows on where _dispatch.wants_rt says so -- never below
-# RT_MIN_ROWS unless force_generic = 2 lifts that floor, never with force_generic = 1 or under an fp32 request -- and where
-# mnf_nsf_ar_bwd_rt_supported has the shape (nsf_ar_rt's shapes with K = 5 or 8).  Under MNF_DETERMINISTIC=1 the route runs
-# mnf_nsf_ar_bwd_rt_det (no atomic sums).  Measured (tools/time_nsf_ar_bwd_rt.py, profiles/r18/nsf_ar_bwd_rt_ab.txt: NSF_AR.inverse +
+# nsf_ar_bwd_rt (csrc/mnf_nsf_ar_bwd_rt.hip; flows.NSF_AR._rt_bwd): OPT-IN (RT_ROUTES "nsf_ar_bwd"; an existing
+# test pins nsf_ar_bwd_generic under force_generic = 2), nsf_ar_rt's shapes with K = 5 or 8.  Under MNF_DETERMINISTIC=1 the route
+# runs mnf_nsf_ar_bwd_rt_det (no atomic sums).  Measured (tools/time_nsf_ar_bwd_rt.py, profiles/r18/nsf_ar_bwd_rt_ab.txt: NSF_AR.inverse +
 # backward through the layer, forward on nsf_ar_rt both times, this route against nsf_ar_bwd_generic, ns per row, at (dim, K,
 # n_h) = (2, 8, 16), (6, 5, 8), (16, 8, 8), (64, 5, 8), (64, 8, 16) and 2,048 / 8,192 / 65,536 / 262,144 rows, the fixed-order form
 # too at 65,536):
@@ -208,12 +203,9 @@ NSF_AR_BWD_RT_MIN_ROWS = None
 
 # NSF_AR, the element-by-element direction (NSF_AR.forward: z -> x, what model.sample() of a model holding an NSF_AR runs
 # through, and the density pass of an NSF_AR used the IAF way round) on the matrix-core kernel nsf_ar_seq_rt
-# (csrc/mnf_nsf_ar_seq_rt.hip; flows.NSF_AR._rt_seq), forward launches only: OPT-IN, with
-# NSF_AR_BWD_RT_MIN_ROWS' semantics.  None: every call stays on nsf_ar_generic, force_generic = 2 included (existing tests pin
-# that kernel for layer.forward under force_generic = 2 and at 4,099 rows); a number sends a call there from that many rows on
-# where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless force_generic = 2 lifts that floor, never with
-# force_generic = 1 or under an fp32 request -- and where mnf_nsf_ar_seq_rt_supported has the shape (dim 2..128, K = 5 or 8,
-# 1..4 hidden layers of widths 4..16).  Its gradients stay on nsf_ar_bwd_generic.
+# (csrc/mnf_nsf_ar_seq_rt.hip; flows.NSF_AR._rt_seq), forward launches only: OPT-IN (RT_ROUTES
+# "nsf_ar_seq"; existing tests pin nsf_ar_generic for layer.forward under force_generic = 2 and at 4,099 rows), dim 2..128,
+# K = 5 or 8, 1..4 hidden layers of widths 4..16.  Its gradients stay on nsf_ar_bwd_generic.
 # Measured (tools/time_nsf_ar_seq_rt.py, profiles/r19/nsf_ar_seq_rt_ab.txt: NSF_AR.forward through the layer under no_grad,
 # nsf_ar_seq_rt against nsf_ar_generic, median of 15 alternating calls, ns per row, at 2,048 / 8,192 / 65,536 / 262,144 rows):
 #   (2, 8, 16)   13.5 against 22.8 | 3.28 / 5.60 | 0.422 / 0.851 | 0.166 / 0.620
@@ -228,11 +220,8 @@ NSF_AR_SEQ_RT_MIN_ROWS = None
 
 # AffineHalfFlow gradients for conditioners whose widest hidden layer has 65 .. 128 units (h_sizes = (128, 128, 128), (96,),
 # ...) on the second size class of the matrix-core kernel ahf_bwd_rt (csrc/mnf_ahf_bwd_rt.hip, the mnf_affine_half_bwd_rt_wide*
-# entries; flows._ahf_bwd_rt_wide): OPT-IN, with NSF_AR_BWD_RT_MIN_ROWS' semantics.  None: every call stays on
-# ahf_bwd_generic, force_generic = 2 included (an existing test pins that kernel for h_sizes = (128,) at 4,096 rows); a number
-# sends a call there from that many rows on where _dispatch.wants_rt says so -- never below RT_MIN_ROWS unless force_generic = 2
-# lifts that floor, never with force_generic = 1 or under an fp32 request -- and where mnf_affine_half_bwd_rt_wide_supported
-# has the shape.  Under MNF_DETERMINISTIC=1 the route runs mnf_affine_half_bwd_rt_wide_det (no atomic sums); with the owner's
+# entries; flows._ahf_bwd_rt_wide): OPT-IN (RT_ROUTES "ahf_bwd_wide"; an existing test pins
+# ahf_bwd_generic for h_sizes = (128,) at 4,096 rows).  Under MNF_DETERMINISTIC=1 the route runs mnf_affine_half_bwd_rt_wide_det (no atomic sums); with the owner's
 # fuse_rt_training a run of such layers trains as one node on the wide stack entries.
 # Measured (tools/time_ahf_bwd_rt_wide.py, profiles/r20/ahf_bwd_rt_wide_ab.txt: forward + backward through the layer, forward on
 # ahf_rt both times, this route against ahf_bwd_generic, median of 15 alternating calls, ns per row, at 2,048 / 8,192 / 65,536 /
@@ -309,6 +298,52 @@ def wants_rt(rows: int, force_generic: int = 0, fp32_request: bool = False) -> b
     return force_generic != 1 and (force_generic == 2 or (rows >= RT_MIN_ROWS and not fp32_request))
 
 
+@dataclass(frozen=True)
+class RtRoute:
+    """One route onto a run-time-shaped kernel that the Python layer decides (rt_route)."""
+    floor: str              # name of the module constant that is its row floor (looked up at every call: tests patch it)
+    query: str              # the library's shape query
+    by_name: bool           # class "by name" (force_generic = 2 alone reaches it, floor None included), else "opt-in"
+    fp32_vetoes_by_name: bool  # an fp32 request vetoes under force_generic = 2 too (False: force_generic = 2 overrides it)
+
+
+# Every Python-decided route, one row each; rt_route below is the ONE rule that reads it -- the layers' predicates
+# (flows.MAF._rt / _rt_seq / _rt_seq_bwd, flows.NSF_AR._rt / _rt_bwd / _rt_seq, flows._ahf_bwd_rt_wide) and tier() ask it.
+# The two classes, for a route with row floor F (its constant) and a layer's force_generic:
+#   by name:  force_generic = 1 never; 2 at ANY row count, F ignored (None too); 0 needs F set, rows >= F,
+#             rows >= RT_MIN_ROWS and no fp32 request.
+#   opt-in:   F None never, rows < F never -- both under force_generic = 2 too; force_generic = 1 never; 2 lifts
+#             RT_MIN_ROWS only; 0 needs rows >= RT_MIN_ROWS and no fp32 request.
+# The last column is what an fp32 request does under force_generic = 2 (without it the request always vetoes: the kernels'
+# arithmetic is split-f16): the MAF family lets force_generic = 2 override it, the later routes do not.  The shape query is
+# asked last in both classes.
+RT_ROUTES = {
+    #                           floor constant              shape query                              by name  fp32 vetoes
+    "maf":            RtRoute("MAF_RT_MIN_ROWS",           "mnf_maf_rt_supported",                  True,    False),
+    "maf_bwd":        RtRoute("MAF_RT_MIN_ROWS",           "mnf_maf_bwd_rt_supported",              True,    False),
+    "maf_seq":        RtRoute("MAF_SEQ_RT_MIN_ROWS",       "mnf_maf_seq_rt_supported",              True,    False),
+    "maf_seq_bwd":    RtRoute("MAF_SEQ_BWD_RT_MIN_ROWS",   "mnf_maf_seq_bwd_rt_supported",          False,   False),
+    "nsf_ar":         RtRoute("NSF_AR_RT_MIN_ROWS",        "mnf_nsf_ar_rt_supported",               True,    True),
+    "nsf_ar_bwd":     RtRoute("NSF_AR_BWD_RT_MIN_ROWS",    "mnf_nsf_ar_bwd_rt_supported",           False,   True),
+    "nsf_ar_seq":     RtRoute("NSF_AR_SEQ_RT_MIN_ROWS",    "mnf_nsf_ar_seq_rt_supported",           False,   True),
+    "ahf_bwd_wide":   RtRoute("AHF_BWD_RT_WIDE_MIN_ROWS",  "mnf_affine_half_bwd_rt_wide_supported", False,   True),
+}
+
+
+def rt_route(name: str, rows: int, shape_args, force_generic: int = 0, fp32_request: bool = False) -> bool:
+    """Does a call of ``rows`` rows take route ``name`` of RT_ROUTES?  ``shape_args``: the arguments of its shape query."""
+    from . import _lib
+    route = RT_ROUTES[name]
+    floor = globals()[route.floor]
+    if fp32_request and route.fp32_vetoes_by_name:
+        return False
+    if not wants_rt(rows, force_generic, fp32_request):
+        return False
+    if not (route.by_name and force_generic == 2) and (floor is None or rows < floor):
+        return False
+    return bool(getattr(_lib.load(), route.query)(*shape_args))
+
+
 def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None = None, scale: bool = True,
          shift: bool = True) -> str:
     """Tier of one layer call (no force_generic, no fp32 request; the same under MNF_DETERMINISTIC=1): kind "ahf" |
@@ -324,30 +359,11 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     if kind == "glow":
         return glow_route(rows, dim, 0, weight=direction == "bwd")
     lib, hid, n = _lib.load(), _lib.int_array(list(hidden)), len(hidden)
-    if kind == "nsf_ar_seq":  # the element-by-element direction: a matrix-core forward kernel, opt-in; gradients on the VALU kernel
-        floor = NSF_AR_SEQ_RT_MIN_ROWS
-        if direction != "fwd" or floor is None or rows < floor or not wants_rt(rows):
+    if kind in ("maf", "maf_seq", "nsf_ar", "nsf_ar_seq"):  # the Python-decided routes: RT_ROUTES, one kernel or the VALU one
+        if kind == "nsf_ar_seq" and direction != "fwd":  # (NSF_AR.forward's gradients have the VALU kernel only)
             return "valu"
-        return "rt" if lib.mnf_nsf_ar_seq_rt_supported(dim, K, n, hid) else "valu"
-    if kind == "nsf_ar":  # the one-pass direction's kernels are opt-in, the forward and the gradient one each by its own constant
-        floor = NSF_AR_RT_MIN_ROWS if direction == "fwd" else NSF_AR_BWD_RT_MIN_ROWS
-        if floor is None or rows < floor or not wants_rt(rows):
-            return "valu"
-        query = lib.mnf_nsf_ar_rt_supported if direction == "fwd" else lib.mnf_nsf_ar_bwd_rt_supported
-        return "rt" if query(dim, K, n, hid) else "valu"
-    if kind == "maf_seq" and direction != "fwd":  # its gradients: the VALU kernel unless the rt route is opted in
-        if MAF_SEQ_BWD_RT_MIN_ROWS is None or rows < MAF_SEQ_BWD_RT_MIN_ROWS or not wants_rt(rows):
-            return "valu"
-        return "rt" if lib.mnf_maf_seq_bwd_rt_supported(dim, n, hid) else "valu"
-    if kind == "maf_seq":  # the element-by-element direction: a matrix-core forward kernel
-        if MAF_SEQ_RT_MIN_ROWS is None or rows < MAF_SEQ_RT_MIN_ROWS or not wants_rt(rows):
-            return "valu"
-        return "rt" if lib.mnf_maf_seq_rt_supported(dim, n, hid) else "valu"
-    if kind == "maf":
-        if MAF_RT_MIN_ROWS is None or rows < MAF_RT_MIN_ROWS or not wants_rt(rows):
-            return "valu"
-        query = lib.mnf_maf_rt_supported if direction == "fwd" else lib.mnf_maf_bwd_rt_supported
-        return "rt" if query(dim, n, hid) else "valu"
+        shape_args = (dim, n, hid) if kind.startswith("maf") else (dim, K, n, hid)
+        return "rt" if rt_route(kind if direction == "fwd" else kind + "_bwd", rows, shape_args) else "valu"
     if kind == "ahf":
         if direction == "fwd":
             per_shape = lib.mnf_affine_half_image_floats(dim, n, hid, int(scale), int(shift)) > 0
@@ -371,8 +387,8 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
     if kind == "ahf":
         query = lib.mnf_affine_half_rt_supported if fwd else lib.mnf_affine_half_bwd_rt_supported
         rt = query(dim, n, hid, int(scale), int(shift))
-        if not rt and not fwd and AHF_BWD_RT_WIDE_MIN_ROWS is not None and rows >= AHF_BWD_RT_WIDE_MIN_ROWS:
-            rt = lib.mnf_affine_half_bwd_rt_wide_supported(dim, n, hid, int(scale), int(shift))  # (opt-in: widest 65 .. 128)
+        if not rt and not fwd:  # (opt-in: widest 65 .. 128)
+            rt = rt_route("ahf_bwd_wide", rows, (dim, n, hid, int(scale), int(shift)))
     elif kind == "nsf":
         rt = (lib.mnf_nsf_cl_rt_supported if fwd else lib.mnf_nsf_cl_bwd_rt_supported)(dim, K, n, hid)
     else:

@@ -230,6 +230,36 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _counted_index(lib, count: str, fill: str, shape: tuple):
+    """An operand index table on the host by the count / allocate / fill protocol: ``count(*shape)`` ints, written by
+    ``fill(*shape, table)``; None where the count is not positive (the shape has no such kernel)."""
+    n = getattr(lib, count)(*shape)
+    if n <= 0:
+        return None
+    idx = (ctypes.c_int32 * n)()
+    _lib.check(fill, getattr(lib, fill)(*shape, idx))
+    return idx
+
+
+def _layout_index(lib, stem: str, shape: tuple):
+    """(host index table, n_split_words, n_plain_words) of a split operand image: ``<stem>_layout(*shape, &n_split,
+    &n_plain)``, then ``<stem>_index(*shape, table)`` into 2 n_split + n_plain ints; None where the layout query answers
+    MNF_ERR_UNSUPPORTED (the shape has no such kernel)."""
+    n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
+    rc = getattr(lib, stem + "_layout")(*shape, ctypes.byref(n_split), ctypes.byref(n_plain))
+    if rc == _lib.MNF_ERR_UNSUPPORTED:
+        return None
+    _lib.check(stem + "_layout", rc)
+    idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
+    _lib.check(stem + "_index", getattr(lib, stem + "_index")(*shape, idx))
+    return idx, n_split.value, n_plain.value
+
+
+def _index_on(device, idx) -> Tensor:
+    """A host index table (ctypes int32 array) as a device tensor."""
+    return torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
+
+
 def _device_input(t: Tensor, what: str) -> Tensor:
     if not isinstance(t, Tensor) or not t.is_cuda:
         raise RuntimeError(
@@ -273,9 +303,32 @@ bwd_kernel_events: list | None = None  # set to a list to collect (start, end) e
 rnvp_bwd_kernel_events: list | None = None  # likewise for launch B-ts of every RNVP gradient pass
 
 
-def _rt_det_workspace(n: int, grad_flat_ptr, device) -> Tensor | None:
-    """The slots of a run-time-shaped gradient launch's fixed-order form (mnf_*_bwd_rt_det; None: no parameter sums)."""
-    return torch.empty(n, dtype=torch.float32, device=device) if grad_flat_ptr is not None else None
+def _bwd_rt_launch(lib, entry: str, args: tuple, shape: tuple, device, sums: bool = True) -> int:
+    """One run-time-shaped gradient launch, the library's code returned: ``entry(*args, stream)`` with atomic parameter
+    sums, or -- MNF_DETERMINISTIC=1 -- the same kernel with fixed-order sums (a slot per workgroup, added up in order):
+    ``<entry>_det_workspace(*shape)`` floats of workspace handed to ``<entry>_det`` behind ``args``; no workspace for the
+    call means MNF_ERR_UNSUPPORTED with nothing launched.  ``sums=False``: the call wants no parameter sums, so no slots."""
+    if not _lib.deterministic():
+        return getattr(lib, entry)(*args, _stream())
+    n = getattr(lib, entry + "_det_workspace")(*shape)
+    if n <= 0:
+        return _lib.MNF_ERR_UNSUPPORTED
+    ws = torch.empty(n, dtype=torch.float32, device=device) if sums else None
+    return getattr(lib, entry + "_det")(*args, _ptr(ws), n if sums else 0, _stream())
+
+
+def _contig(t: Tensor | None) -> Tensor | None:
+    """A cotangent as the kernels take it: contiguous, or None where autograd handed none."""
+    return None if t is None else t.contiguous()
+
+
+def _grad_home(home: tuple | None, flat: Tensor) -> tuple[Tensor, Tensor | None]:
+    """(the tensor a backward pass adds the flat parameter gradient to, what it returns for the flat input): the gradient
+    slice of the flat home (see _flat_home_of) and None, else one fresh zero vector as both."""
+    if home is not None:
+        return home[0].grad[home[1]:home[1] + home[2]], None
+    grad_flat = torch.zeros_like(flat)
+    return grad_flat, grad_flat
 
 
 def _bwd_split_workspace(lib, f, rows: int, device) -> Tensor | None:
@@ -352,22 +405,11 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
         sc = scale if scale is not None else _grad_scale(gy, gl, rows, f.dim, x_in.device)
         args = (x_in.data_ptr(), _ptr(y_out), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, sc.data_ptr(),
                 rows, f.dim, int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift))
-        if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
-            n_ws = lib.mnf_affine_half_bwd_rt_det_workspace(rows, f.dim, *hid, int(f.scale), int(f.shift))
-            if n_ws > 0:
-                ws = _rt_det_workspace(n_ws, grad_flat_ptr, x_in.device)
-                rc = lib.mnf_affine_half_bwd_rt_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
-        else:
-            rc = lib.mnf_affine_half_bwd_rt(*args, _stream())
+        ws_shape, sums = (rows, f.dim, *hid, int(f.scale), int(f.shift)), grad_flat_ptr is not None
+        rc = _bwd_rt_launch(lib, "mnf_affine_half_bwd_rt", args, ws_shape, x_in.device, sums)
         if rc == _lib.MNF_ERR_UNSUPPORTED and _ahf_bwd_rt_wide(lib, f, rows):
             # widest hidden layer 65 .. 128 units: the kernel's second size class (opt-in, the same arguments)
-            if _lib.deterministic():
-                n_ws = lib.mnf_affine_half_bwd_rt_wide_det_workspace(rows, f.dim, *hid, int(f.scale), int(f.shift))
-                if n_ws > 0:
-                    ws = _rt_det_workspace(n_ws, grad_flat_ptr, x_in.device)
-                    rc = lib.mnf_affine_half_bwd_rt_wide_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
-            else:
-                rc = lib.mnf_affine_half_bwd_rt_wide(*args, _stream())
+            rc = _bwd_rt_launch(lib, "mnf_affine_half_bwd_rt_wide", args, ws_shape, x_in.device, sums)
     if rc == _lib.MNF_ERR_UNSUPPORTED:  # no matrix-core gradient kernel for this shape at all
         rc = lib.mnf_affine_half_bwd(
             x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, rows, f.dim,
@@ -383,15 +425,10 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
 
 def _ahf_bwd_rt_wide(lib, f, rows: int) -> bool:
     """Do the gradients of an AffineHalfFlow call whose widest hidden layer has 65 .. 128 units go to the matrix-core kernel's
-    wide entries (mnf_affine_half_bwd_rt_wide*)?  Opt-in, as NSF_AR._rt_bwd: only with _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS set
-    (None: never -- force_generic = 2 alone does not select it), from that many rows on, where _dispatch.wants_rt says so
-    (force_generic = 2 lifts its row floor, 1 vetoes), never under an fp32 request, and where the library has the shape."""
-    floor = _dispatch.AHF_BWD_RT_WIDE_MIN_ROWS
-    if floor is None or rows < floor:
-        return False
-    if f._fp32_request() or not _dispatch.wants_rt(rows, int(f.force_generic), False):
-        return False
-    return bool(lib.mnf_affine_half_bwd_rt_wide_supported(f.dim, len(f.h_sizes), f._hid, int(f.scale), int(f.shift)))
+    wide entries (mnf_affine_half_bwd_rt_wide*)?  _dispatch.RT_ROUTES "ahf_bwd_wide": opt-in.  (``lib`` is kept for the
+    callers' sake: the route rule asks the loaded library itself.)"""
+    return _dispatch.rt_route("ahf_bwd_wide", rows, (f.dim, len(f.h_sizes), f._hid, int(f.scale), int(f.shift)),
+                              int(f.force_generic), f._fp32_request())
 
 
 class _AffineHalfFn(torch.autograd.Function):
@@ -419,8 +456,8 @@ class _AffineHalfFn(torch.autograd.Function):
     def backward(ctx, grad_y, grad_ld):
         x, flat, y_out = ctx.saved_tensors
         m = ctx.module
-        gy = None if grad_y is None else grad_y.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gy = _contig(grad_y)
+        gl = _contig(grad_ld)
         grad_x = torch.empty_like(x)
         grad_flat = torch.zeros_like(flat)
         has = flat.numel() > 0
@@ -462,8 +499,8 @@ class _NsfFn(torch.autograd.Function):
     def backward(ctx, grad_y, grad_ld):
         x, flat, y_out = ctx.saved_tensors
         m = ctx.module
-        gy = None if grad_y is None else grad_y.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gy = _contig(grad_y)
+        gl = _contig(grad_ld)
         grad_x = torch.empty_like(x)
         grad_flat = torch.zeros_like(flat)
         lib = _lib.load()
@@ -508,14 +545,7 @@ class _NsfFn(torch.autograd.Function):
             scale = _grad_scale(gy, gl, rows, m.dim, x.device)
             rt_args = (x.data_ptr(), y_out.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(),
                        flat.data_ptr(), scale.data_ptr(), *args)
-            rc = _lib.MNF_ERR_UNSUPPORTED
-            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
-                n_ws = lib.mnf_nsf_cl_bwd_rt_det_workspace(rows, m.dim, m.K, len(m.h_sizes), m._hid)
-                if n_ws > 0:
-                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
-                    rc = lib.mnf_nsf_cl_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
-            else:
-                rc = lib.mnf_nsf_cl_bwd_rt(*rt_args, _stream())
+            rc = _bwd_rt_launch(lib, "mnf_nsf_cl_bwd_rt", rt_args, (rows, m.dim, m.K, len(m.h_sizes), m._hid), x.device)
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_nsf_cl_bwd_rt", rc)
                 return grad_x, grad_flat, None, None
@@ -564,17 +594,14 @@ class _RnvpFn(torch.autograd.Function):
     def backward(ctx, grad_x, grad_ld):
         z, flat = ctx.saved_tensors
         m = ctx.module
-        gx = None if grad_x is None else grad_x.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gx = _contig(grad_x)
+        gl = _contig(grad_ld)
         grad_z = torch.empty_like(z)
         home = ctx.home
         lib = _lib.load()
         if gx is None and gl is None:
             return grad_z.zero_(), (None if home is not None else torch.zeros_like(flat)), None, None, None, None
-        if home is not None:
-            grad_flat, ret_flat = home[0].grad[home[1]:home[1] + home[2]], None
-        else:
-            grad_flat = ret_flat = torch.zeros_like(flat)
+        grad_flat, ret_flat = _grad_home(home, flat)
         # the matrix-core gradient kernels (two launches + the fp32 fix-up over flagged row groups); shapes they do not
         # cover, the fp32 switches and force_generic take the generic kernel
         # (few rows or a narrow layer: the one-launch generic kernel is the faster one -- the matrix-core pass is four
@@ -622,14 +649,7 @@ class _RnvpFn(torch.autograd.Function):
             scale = _grad_scale(gx, gl, z.shape[0], m.dim, z.device)
             rt_args = (z.data_ptr(), _ptr(ctx.mask), ctx.seed, _ptr(gx), _ptr(gl), grad_z.data_ptr(), grad_flat.data_ptr(),
                        flat.data_ptr(), scale.data_ptr(), z.shape[0], m.dim, len(m.h_sizes), m._hid)
-            rc = _lib.MNF_ERR_UNSUPPORTED
-            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
-                n_ws = lib.mnf_rnvp_bwd_rt_det_workspace(z.shape[0], m.dim, len(m.h_sizes), m._hid)
-                if n_ws > 0:
-                    ws = _rt_det_workspace(n_ws, grad_flat, z.device)
-                    rc = lib.mnf_rnvp_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
-            else:
-                rc = lib.mnf_rnvp_bwd_rt(*rt_args, _stream())
+            rc = _bwd_rt_launch(lib, "mnf_rnvp_bwd_rt", rt_args, (z.shape[0], m.dim, len(m.h_sizes), m._hid), z.device)
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_rnvp_bwd_rt", rc)
                 return grad_z, ret_flat, None, None, None, None
@@ -723,13 +743,8 @@ def _linear_rows_image(lib, W: Tensor, table: Tensor) -> Tensor:
 def _linear_rows_table(lib, dim: int, device) -> Tensor | None:
     key = (dim, device)
     if key not in _LINEAR_ROWS_INDEX:
-        n = lib.mnf_linear_rows_image_floats(dim)
-        table = None
-        if n > 0:
-            idx = (ctypes.c_int32 * n)()
-            _lib.check("mnf_linear_rows_image_index", lib.mnf_linear_rows_image_index(dim, idx))
-            table = torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
-        _LINEAR_ROWS_INDEX[key] = table
+        idx = _counted_index(lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (dim,))
+        _LINEAR_ROWS_INDEX[key] = None if idx is None else _index_on(device, idx)
     return _LINEAR_ROWS_INDEX[key]
 
 
@@ -799,7 +814,7 @@ class _GlowActNormInvFn(torch.autograd.Function):
         u, Mc, sc, tc = ctx.saved_tensors[:4]
         dim = u.shape[1]
         gz = torch.zeros_like(u) if grad_z is None else grad_z.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gl = _contig(grad_ld)
         gu = torch.empty_like(u)
         sums = torch.zeros(dim * dim + 2 * dim, dtype=torch.float32, device=u.device)  # grad_M | grad_s | grad_t
         gM, gs, gt = sums[:dim * dim], sums[dim * dim:dim * dim + dim], sums[dim * dim + dim:]
@@ -947,9 +962,8 @@ class _AffineRunFn(torch.autograd.Function):
         inputs = [x] + list(mids)                     # input of the li-th applied layer
         order = list(reversed(run.layers)) if inverse else list(run.layers)
         grad_ld = grads[-1]
-        gl = None if grad_ld is None else grad_ld.contiguous()
-        home = ctx.home
-        grad_flat = home[0].grad[home[1]:home[1] + home[2]] if home is not None else torch.zeros_like(flat)
+        gl = _contig(grad_ld)
+        grad_flat, ret_flat = _grad_home(ctx.home, flat)
         # offset of every layer's parameters inside the run's flat vector (model order)
         sizes = [sum(p.numel() for p in f._packed_params()) for f in run.layers]
         offs = [0]
@@ -980,10 +994,10 @@ class _AffineRunFn(torch.autograd.Function):
                 if not done:
                     g = z_last * (-gl).unsqueeze(1)
             if not done:
-                gy = None if g is None else g.contiguous()
+                gy = _contig(g)
                 _ahf_layer_backward(lib, f, inputs[li], gy, gl, gx, *args)
             g = gx if li == 0 or grads[li - 1] is None else gx + grads[li - 1]
-        return g, (None if home is not None else grad_flat), None, None, None
+        return g, ret_flat, None, None, None
 
 
     @staticmethod
@@ -998,7 +1012,7 @@ class _AffineRunFn(torch.autograd.Function):
             if grads[0] is None:
                 return None, None, None, None, None
             grads = (None,) * n + (grads[0],)
-        gl = None if grads[-1] is None else grads[-1].contiguous()
+        gl = _contig(grads[-1])
         home = ctx.home
         want_flat = home is not None or ctx.needs_input_grad[1]
         grad_flat = (home[0].grad[home[1]:home[1] + home[2]] if home is not None
@@ -1007,19 +1021,15 @@ class _AffineRunFn(torch.autograd.Function):
         hid = (len(f0.h_sizes), f0._hid)
         gx = torch.empty_like(x)
         one_launch = all(g is None for g in grads[:n - 1])
-        n_ws = 0
-        # the run's entries: the wide ones where the widest hidden layer has 65 .. 128 units (rt_train_route let it in)
-        wide = not lib.mnf_affine_half_bwd_rt_stack_supported(f0.dim, *hid, int(f0.scale), int(f0.shift), n)
-        stack_ws, stack_det, stack_bwd = (
-            (lib.mnf_affine_half_bwd_rt_wide_stack_det_workspace, lib.mnf_affine_half_bwd_rt_wide_stack_det,
-             lib.mnf_affine_half_bwd_rt_wide_stack) if wide else
-            (lib.mnf_affine_half_bwd_rt_stack_det_workspace, lib.mnf_affine_half_bwd_rt_stack_det,
-             lib.mnf_affine_half_bwd_rt_stack))
+        # the run's entry: the wide one where the widest hidden layer has 65 .. 128 units (rt_train_route let it in)
+        ws_shape = (rows, f0.dim, *hid, int(f0.scale), int(f0.shift), n)
+        entry = ("mnf_affine_half_bwd_rt_stack" if lib.mnf_affine_half_bwd_rt_stack_supported(*ws_shape[1:])
+                 else "mnf_affine_half_bwd_rt_wide_stack")
         if one_launch and _lib.deterministic() and grad_flat is not None:
-            n_ws = stack_ws(rows, f0.dim, *hid, int(f0.scale), int(f0.shift), n)
-            one_launch = n_ws > 0  # (no fixed-order launch for the call: the layers one by one, as they do by themselves)
+            # (no fixed-order launch for the call: the layers one by one, as they do by themselves)
+            one_launch = getattr(lib, entry + "_det_workspace")(*ws_shape) > 0
         if one_launch:
-            g_last = None if grads[n - 1] is None else grads[n - 1].contiguous()
+            g_last = _contig(grads[n - 1])
             lp_grad, gy, gld = (gl, None, None) if ctx.with_lp else (None, g_last, gl)
             scale = _rt_layer_scales(lib, run, x, buf, flat, g_last, gl, ctx.with_lp, inverse)
             work = torch.empty_like(x) if n > 1 else None
@@ -1027,12 +1037,8 @@ class _AffineRunFn(torch.autograd.Function):
             args = (x.data_ptr(), buf.data_ptr(), _ptr(gy), _ptr(lp_grad), _ptr(gld), gx.data_ptr(), _ptr(work),
                     _ptr(grad_flat), flat.data_ptr(), scale.data_ptr(), par, n, rows, f0.dim, int(inverse), *hid,
                     int(f0.scale), int(f0.shift))
-            if _lib.deterministic():
-                ws = _rt_det_workspace(n_ws, _ptr(grad_flat), dev)
-                rc = stack_det(*args, _ptr(ws), 0 if ws is None else n_ws, _stream())
-            else:
-                rc = stack_bwd(*args, _stream())
-            _lib.check("mnf_affine_half_bwd_rt_stack", rc)
+            _lib.check("mnf_affine_half_bwd_rt_stack",
+                       _bwd_rt_launch(lib, entry, args, ws_shape, dev, sums=grad_flat is not None))
             g = gx
         else:
             order = list(reversed(run.layers)) if inverse else list(run.layers)
@@ -1132,15 +1138,14 @@ class _HipFlow(nn.Module):
         """Device copy of the fp32 operand-image index table (built once), or None."""
         if self._index is None or self._index.device != device:
             host = self._image_index_host()
-            self._index = None if host is None else torch.frombuffer(host, dtype=torch.int32).clone().to(device)
+            self._index = None if host is None else _index_on(device, host)
         return self._index
 
     def _device_split_index(self, device: torch.device):
         """(device index table, n_split_words, n_plain_words) of the split operand image, or False."""
         if self._split_index is None or (self._split_index and self._split_index[0].device != device):
             host = self._split_index_host()
-            self._split_index = False if host is None else (
-                torch.frombuffer(host[0], dtype=torch.int32).clone().to(device), host[1], host[2])
+            self._split_index = False if host is None else (_index_on(device, host[0]), host[1], host[2])
         return self._split_index
 
     def _packed(self, device: torch.device, images: bool = True) -> tuple[Tensor | None, Tensor | None]:
@@ -1224,32 +1229,20 @@ class AffineHalfFlow(_TwoWayFlow):
     def _packed_params(self) -> list[Tensor]:
         return self._net_params(([self.s_net] if self.scale else []) + ([self.t_net] if self.shift else []))
 
+    def _shape(self) -> tuple:
+        """The shape arguments of the library's index-table entries."""
+        return self.dim, len(self.h_sizes), self._hid, self.scale, self.shift
+
     def _image_index_host(self):
-        lib = _lib.load()
-        n = lib.mnf_affine_half_image_floats(self.dim, len(self.h_sizes), self._hid, self.scale, self.shift)
-        if n <= 0:
-            return None
-        idx = (ctypes.c_int32 * n)()
-        _lib.check("mnf_affine_half_image_index", lib.mnf_affine_half_image_index(
-            self.dim, len(self.h_sizes), self._hid, self.scale, self.shift, idx))
-        return idx
+        return _counted_index(_lib.load(), "mnf_affine_half_image_floats", "mnf_affine_half_image_index", self._shape())
 
     def _bwd_split_index(self, device):
         """(device index table, n_split_words, n_plain_words) of the split gradient kernel's operand image (forward
         and transposed weights), built once per module; False: no such kernel for this shape."""
         cached = self.__dict__.get("_bwd_split_index_cache")
         if cached is None or (cached and cached[0].device != device):
-            lib = _lib.load()
-            n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-            rc = lib.mnf_affine_half_bwd_split_layout(self.dim, len(self.h_sizes), self._hid, self.scale, self.shift,
-                                                      ctypes.byref(n_split), ctypes.byref(n_plain))
-            cached = False
-            if rc != _lib.MNF_ERR_UNSUPPORTED:
-                _lib.check("mnf_affine_half_bwd_split_layout", rc)
-                idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-                _lib.check("mnf_affine_half_bwd_split_index", lib.mnf_affine_half_bwd_split_index(
-                    self.dim, len(self.h_sizes), self._hid, self.scale, self.shift, idx))
-                cached = (torch.frombuffer(idx, dtype=torch.int32).clone().to(device), n_split.value, n_plain.value)
+            host = _layout_index(_lib.load(), "mnf_affine_half_bwd_split", self._shape())
+            cached = False if host is None else (_index_on(device, host[0]), host[1], host[2])
             self.__dict__["_bwd_split_index_cache"] = cached
         return cached
 
@@ -1274,30 +1267,13 @@ class AffineHalfFlow(_TwoWayFlow):
         """Device index table of the MFMA gradient kernel (built once per module), or None."""
         cached = self.__dict__.get("_bwd_index_cache")
         if cached is None or (cached[0] is not None and cached[0].device != device):
-            lib = _lib.load()
-            n = lib.mnf_affine_half_bwd_index_ints(self.dim, len(self.h_sizes), self._hid, self.scale, self.shift)
-            table = None
-            if n > 0:
-                idx = (ctypes.c_int32 * n)()
-                _lib.check("mnf_affine_half_bwd_index", lib.mnf_affine_half_bwd_index(
-                    self.dim, len(self.h_sizes), self._hid, self.scale, self.shift, idx))
-                table = torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
-            cached = (table,)
+            idx = _counted_index(_lib.load(), "mnf_affine_half_bwd_index_ints", "mnf_affine_half_bwd_index", self._shape())
+            cached = (None if idx is None else _index_on(device, idx),)
             self.__dict__["_bwd_index_cache"] = cached
         return cached[0]
 
     def _split_index_host(self):
-        lib = _lib.load()
-        n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-        rc = lib.mnf_affine_half_split_layout(self.dim, len(self.h_sizes), self._hid, self.scale, self.shift,
-                                              ctypes.byref(n_split), ctypes.byref(n_plain))
-        if rc == _lib.MNF_ERR_UNSUPPORTED:
-            return None
-        _lib.check("mnf_affine_half_split_layout", rc)
-        idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-        _lib.check("mnf_affine_half_split_index", lib.mnf_affine_half_split_index(
-            self.dim, len(self.h_sizes), self._hid, self.scale, self.shift, idx))
-        return idx, n_split.value, n_plain.value
+        return _layout_index(_lib.load(), "mnf_affine_half_split", self._shape())
 
     def _run(self, x, inverse, accum, sqnorm: Tensor | None = None, overwrite: bool = False):
         # overwrite: accum receives ld instead of += ld (first layer of a pass: saves zero-filling it)
@@ -1367,27 +1343,11 @@ class NSF_CL(_TwoWayFlow):
         return self._net_params([self.f1, self.f2])
 
     def _image_index_host(self):
-        lib = _lib.load()
-        n = lib.mnf_nsf_cl_image_floats(self.dim, self.K, len(self.h_sizes), self._hid)
-        if n <= 0:
-            return None
-        idx = (ctypes.c_int32 * n)()
-        _lib.check("mnf_nsf_cl_image_index", lib.mnf_nsf_cl_image_index(
-            self.dim, self.K, len(self.h_sizes), self._hid, idx))
-        return idx
+        return _counted_index(_lib.load(), "mnf_nsf_cl_image_floats", "mnf_nsf_cl_image_index",
+                              (self.dim, self.K, len(self.h_sizes), self._hid))
 
     def _split_index_host(self):
-        lib = _lib.load()
-        n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-        rc = lib.mnf_nsf_cl_split_layout(self.dim, self.K, len(self.h_sizes), self._hid, ctypes.byref(n_split),
-                                         ctypes.byref(n_plain))
-        if rc == _lib.MNF_ERR_UNSUPPORTED:
-            return None
-        _lib.check("mnf_nsf_cl_split_layout", rc)
-        idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-        _lib.check("mnf_nsf_cl_split_index", lib.mnf_nsf_cl_split_index(
-            self.dim, self.K, len(self.h_sizes), self._hid, idx))
-        return idx, n_split.value, n_plain.value
+        return _layout_index(_lib.load(), "mnf_nsf_cl_split", (self.dim, self.K, len(self.h_sizes), self._hid))
 
     def _bwd_tile_tables(self, device):
         """(operand index table, flush table, n_split_words, n_plain_words) of the tile gradient kernel on the device,
@@ -1405,8 +1365,7 @@ class NSF_CL(_TwoWayFlow):
                 flush = (ctypes.c_int32 * n_params.value)()
                 _lib.check("mnf_nsf_cl_bwd_tile_index", lib.mnf_nsf_cl_bwd_tile_index(
                     self.dim, self.K, len(self.h_sizes), self._hid, idx, flush))
-                cached = (torch.frombuffer(idx, dtype=torch.int32).clone().to(device),
-                          torch.frombuffer(flush, dtype=torch.int32).clone().to(device), n_split.value, n_plain.value)
+                cached = (_index_on(device, idx), _index_on(device, flush), n_split.value, n_plain.value)
             self.__dict__["_bwd_tile_cache"] = cached
         return cached
 
@@ -1527,8 +1486,8 @@ class _NsfArFn(torch.autograd.Function):
     def backward(ctx, grad_y, grad_ld):
         x, flat = ctx.saved_tensors
         m = ctx.module
-        gy = None if grad_y is None else grad_y.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gy = _contig(grad_y)
+        gl = _contig(grad_ld)
         grad_x = torch.empty_like(x)
         grad_flat = torch.zeros_like(flat)
         lib, rows = _lib.load(), x.shape[0]
@@ -1536,14 +1495,7 @@ class _NsfArFn(torch.autograd.Function):
             # the one-pass direction on the matrix cores; under MNF_DETERMINISTIC=1 its fixed-order form
             rt_args = (x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), rows,
                        m.dim, m.K, float(m.B), len(m.h_sizes), m._hid)
-            rc = _lib.MNF_ERR_UNSUPPORTED
-            if _lib.deterministic():
-                n_ws = lib.mnf_nsf_ar_bwd_rt_det_workspace(rows, m.dim, m.K, len(m.h_sizes), m._hid)
-                if n_ws > 0:
-                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
-                    rc = lib.mnf_nsf_ar_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
-            else:
-                rc = lib.mnf_nsf_ar_bwd_rt(*rt_args, _stream())
+            rc = _bwd_rt_launch(lib, "mnf_nsf_ar_bwd_rt", rt_args, (rows, m.dim, m.K, len(m.h_sizes), m._hid), x.device)
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_nsf_ar_bwd_rt", rc)
                 return grad_x, grad_flat, None, None
@@ -1589,41 +1541,24 @@ class NSF_AR(_TwoWayFlow):
         return [self.init_param] + self._net_params(list(self.layers))
 
     def _rt(self, rows: int) -> bool:
-        """Does a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_rt?  As MAF._rt_seq: where
-        _dispatch.wants_rt says so (never with force_generic = 1) and never under an fp32 request, from
-        _dispatch.NSF_AR_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2 alone), and where the library has the
-        shape.  Forward launches only: the gradients stay on mnf_nsf_ar_bwd, which recomputes from x."""
-        force = int(self.force_generic)
-        if self._fp32_request() or not _dispatch.wants_rt(rows, force, False):  # (split-f16 arithmetic: not even by name)
-            return False
-        if force != 2 and (_dispatch.NSF_AR_RT_MIN_ROWS is None or rows < _dispatch.NSF_AR_RT_MIN_ROWS):
-            return False
-        return bool(_lib.load().mnf_nsf_ar_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+        """Does a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_rt?  _dispatch.RT_ROUTES "nsf_ar":
+        by name.  Forward launches only: the gradients stay on mnf_nsf_ar_bwd, which recomputes from x."""
+        return self._route("nsf_ar", rows)
 
     def _rt_bwd(self, rows: int) -> bool:
-        """Do the gradients of a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_bwd_rt?  Opt-in, as
-        MAF._rt_seq_bwd: only with _dispatch.NSF_AR_BWD_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not
-        select it), from that many rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1
-        vetoes), never under an fp32 request, and where the library has the shape."""
-        floor = _dispatch.NSF_AR_BWD_RT_MIN_ROWS
-        if floor is None or rows < floor:
-            return False
-        if self._fp32_request() or not _dispatch.wants_rt(rows, int(self.force_generic), False):
-            return False
-        return bool(_lib.load().mnf_nsf_ar_bwd_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+        """Do the gradients of a one-pass call (NSF_AR.inverse) go to the matrix-core kernel nsf_ar_bwd_rt?
+        _dispatch.RT_ROUTES "nsf_ar_bwd": opt-in."""
+        return self._route("nsf_ar_bwd", rows)
 
     def _rt_seq(self, rows: int) -> bool:
-        """Does an element-by-element call (NSF_AR.forward: sampling) go to the matrix-core kernel nsf_ar_seq_rt?  Opt-in,
-        as _rt_bwd: only with _dispatch.NSF_AR_SEQ_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not
-        select it), from that many rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1
-        vetoes), never under an fp32 request, and where the library has the shape.  Forward launches only: the gradients
-        stay on mnf_nsf_ar_bwd, which recomputes from its input."""
-        floor = _dispatch.NSF_AR_SEQ_RT_MIN_ROWS
-        if floor is None or rows < floor:
-            return False
-        if self._fp32_request() or not _dispatch.wants_rt(rows, int(self.force_generic), False):
-            return False
-        return bool(_lib.load().mnf_nsf_ar_seq_rt_supported(self.dim, self.K, len(self.h_sizes), self._hid))
+        """Does an element-by-element call (NSF_AR.forward: sampling) go to the matrix-core kernel nsf_ar_seq_rt?
+        _dispatch.RT_ROUTES "nsf_ar_seq": opt-in.  Forward launches only: the gradients stay on mnf_nsf_ar_bwd, which
+        recomputes from its input."""
+        return self._route("nsf_ar_seq", rows)
+
+    def _route(self, name: str, rows: int) -> bool:
+        return _dispatch.rt_route(name, rows, (self.dim, self.K, len(self.h_sizes), self._hid), int(self.force_generic),
+                                  self._fp32_request())
 
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, inverse: bool) -> None:
         """One forward launch: mnf_nsf_ar_rt where `inverse` and _rt says so, mnf_nsf_ar_seq_rt where not `inverse` and
@@ -1708,41 +1643,18 @@ class RNVP(_HipFlow):
         return self._net_params([self.net, self.t, self.s])
 
     def _image_index_host(self):
-        lib = _lib.load()
-        n = lib.mnf_rnvp_image_floats(self.dim, len(self.h_sizes), self._hid)
-        if n <= 0:
-            return None
-        idx = (ctypes.c_int32 * n)()
-        _lib.check("mnf_rnvp_image_index", lib.mnf_rnvp_image_index(self.dim, len(self.h_sizes), self._hid, idx))
-        return idx
+        return _counted_index(_lib.load(), "mnf_rnvp_image_floats", "mnf_rnvp_image_index",
+                              (self.dim, len(self.h_sizes), self._hid))
 
     def _split_index_host(self):
-        lib = _lib.load()
-        n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-        rc = lib.mnf_rnvp_split_layout(self.dim, len(self.h_sizes), self._hid, ctypes.byref(n_split),
-                                       ctypes.byref(n_plain))
-        if rc == _lib.MNF_ERR_UNSUPPORTED:
-            return None
-        _lib.check("mnf_rnvp_split_layout", rc)
-        idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-        _lib.check("mnf_rnvp_split_index", lib.mnf_rnvp_split_index(self.dim, len(self.h_sizes), self._hid, idx))
-        return idx, n_split.value, n_plain.value
+        return _layout_index(_lib.load(), "mnf_rnvp_split", (self.dim, len(self.h_sizes), self._hid))
 
     def _bwd_index(self, device):
         """(device index table, n_split_words, n_plain_words) of the gradient kernels' operand image, or False."""
         cached = self.__dict__.get("_bwd_idx")
         if cached is None or (cached and cached[0].device != device):
-            lib = _lib.load()
-            n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-            rc = lib.mnf_rnvp_bwd_mfma_layout(self.dim, len(self.h_sizes), self._hid, ctypes.byref(n_split),
-                                              ctypes.byref(n_plain))
-            if rc == _lib.MNF_ERR_UNSUPPORTED:
-                cached = False
-            else:
-                _lib.check("mnf_rnvp_bwd_mfma_layout", rc)
-                idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-                _lib.check("mnf_rnvp_bwd_mfma_index", lib.mnf_rnvp_bwd_mfma_index(self.dim, len(self.h_sizes), self._hid, idx))
-                cached = (torch.frombuffer(idx, dtype=torch.int32).clone().to(device), n_split.value, n_plain.value)
+            host = _layout_index(_lib.load(), "mnf_rnvp_bwd_mfma", (self.dim, len(self.h_sizes), self._hid))
+            cached = False if host is None else (_index_on(device, host[0]), host[1], host[2])
             self.__dict__["_bwd_idx"] = cached
         return cached
 
@@ -1878,27 +1790,17 @@ class _MafFn(torch.autograd.Function):
     def backward(ctx, grad_y, grad_ld):
         x, y, flat, masks = ctx.saved_tensors
         m, home = ctx.module, ctx.home
-        gy = None if grad_y is None else grad_y.contiguous()
-        gl = None if grad_ld is None else grad_ld.contiguous()
+        gy = _contig(grad_y)
+        gl = _contig(grad_ld)
         grad_x = torch.empty_like(x)
-        if home is not None:
-            grad_flat, ret = home[0].grad[home[1]:home[1] + home[2]], None
-        else:
-            grad_flat = ret = torch.zeros_like(flat)
+        grad_flat, ret = _grad_home(home, flat)
         lib, rows = _lib.load(), x.shape[0]
         if m._rt(rows, ctx.sequential, bwd=True):
             # the one-pass direction on the run-time-shaped matrix-core kernel (1..4 hidden layers of widths 4..64)
             scale = _grad_scale(gy, gl, rows, m.dim, x.device)
             rt_args = (x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(),
                        masks.data_ptr(), scale.data_ptr(), rows, m.dim, int(bool(m.parity)), len(m.h_sizes), m._hid)
-            rc = _lib.MNF_ERR_UNSUPPORTED
-            if _lib.deterministic():  # the same kernel with fixed-order sums (a slot per workgroup, added up in order)
-                n_ws = lib.mnf_maf_bwd_rt_det_workspace(rows, m.dim, len(m.h_sizes), m._hid)
-                if n_ws > 0:
-                    ws = _rt_det_workspace(n_ws, grad_flat, x.device)
-                    rc = lib.mnf_maf_bwd_rt_det(*rt_args, ws.data_ptr(), n_ws, _stream())
-            else:
-                rc = lib.mnf_maf_bwd_rt(*rt_args, _stream())
+            rc = _bwd_rt_launch(lib, "mnf_maf_bwd_rt", rt_args, (rows, m.dim, len(m.h_sizes), m._hid), x.device)
             if rc != _lib.MNF_ERR_UNSUPPORTED:
                 _lib.check("mnf_maf_bwd_rt", rc)
                 return grad_x, ret, None, None, None
@@ -1987,43 +1889,25 @@ class MAF(_TwoWayFlow):
         return cached[1]
 
     def _rt(self, rows: int, sequential: bool, bwd: bool = False) -> bool:
-        """Does this call go to the run-time-shaped matrix-core kernels?  The one-pass direction only; where
-        _dispatch.wants_rt says so (not under an fp32 request, never with force_generic = 1), from
-        _dispatch.MAF_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2 alone), and where the library has the shape."""
-        if sequential:
-            return False
-        force = int(self.force_generic)
-        if not _dispatch.wants_rt(rows, force, self._fp32_request()):
-            return False
-        if force != 2 and (_dispatch.MAF_RT_MIN_ROWS is None or rows < _dispatch.MAF_RT_MIN_ROWS):
-            return False
-        lib = _lib.load()
-        query = lib.mnf_maf_bwd_rt_supported if bwd else lib.mnf_maf_rt_supported
-        return bool(query(self.dim, len(self.h_sizes), self._hid))
+        """Does this call go to the run-time-shaped matrix-core kernels?  The one-pass direction only;
+        _dispatch.RT_ROUTES "maf" / "maf_bwd": by name."""
+        return not sequential and self._route("maf_bwd" if bwd else "maf", rows)
 
     def _rt_seq(self, rows: int) -> bool:
-        """Does an element-by-element call (MAF.forward, IAF.inverse) go to the matrix-core kernel maf_seq_rt?  As _rt:
-        where _dispatch.wants_rt says so, from _dispatch.MAF_SEQ_RT_MIN_ROWS rows on (None: opt-in -- force_generic = 2
-        alone), and where the library has the shape (a net that stays resident in LDS).  Forward launches only: the
-        gradients of this direction stay on mnf_maf_bwd."""
-        force = int(self.force_generic)
-        if not _dispatch.wants_rt(rows, force, self._fp32_request()):
-            return False
-        if force != 2 and (_dispatch.MAF_SEQ_RT_MIN_ROWS is None or rows < _dispatch.MAF_SEQ_RT_MIN_ROWS):
-            return False
-        return bool(_lib.load().mnf_maf_seq_rt_supported(self.dim, len(self.h_sizes), self._hid))
+        """Does an element-by-element call (MAF.forward, IAF.inverse) go to the matrix-core kernel maf_seq_rt (a net that
+        stays resident in LDS)?  _dispatch.RT_ROUTES "maf_seq": by name.  Forward launches only: the gradients of this
+        direction stay on mnf_maf_bwd unless _rt_seq_bwd says otherwise."""
+        return self._route("maf_seq", rows)
 
     def _rt_seq_bwd(self, rows: int) -> bool:
-        """Do the gradients of an element-by-element call go to the matrix-core route maf_seq_bwd_rt?  Opt-in: only with
-        _dispatch.MAF_SEQ_BWD_RT_MIN_ROWS set (None: never -- force_generic = 2 alone does not select it), from that many
-        rows on, where _dispatch.wants_rt says so (force_generic = 2 lifts its row floor, 1 vetoes, as does an fp32
-        request) and where the library has the shape."""
-        floor = _dispatch.MAF_SEQ_BWD_RT_MIN_ROWS
-        if floor is None or rows < floor:
-            return False
-        if not _dispatch.wants_rt(rows, int(self.force_generic), self._fp32_request()):
-            return False
-        return bool(_lib.load().mnf_maf_seq_bwd_rt_supported(self.dim, len(self.h_sizes), self._hid))
+        """Do the gradients of an element-by-element call go to the matrix-core route maf_seq_bwd_rt?
+        _dispatch.RT_ROUTES "maf_seq_bwd": opt-in.  As in the whole MAF family an fp32 request vetoes only without
+        force_generic = 2, which overrides it (the route table's last column)."""
+        return self._route("maf_seq_bwd", rows)
+
+    def _route(self, name: str, rows: int) -> bool:
+        return _dispatch.rt_route(name, rows, (self.dim, len(self.h_sizes), self._hid), int(self.force_generic),
+                                  self._fp32_request())
 
     def _launch(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, flat: Tensor, masks: Tensor, sequential: bool) -> None:
         """One forward launch: mnf_maf_rt / mnf_maf_seq_rt where _rt / _rt_seq says so, else mnf_maf (an UNSUPPORTED
@@ -2183,8 +2067,8 @@ class _GlowWeightFn(torch.autograd.Function):
     def backward(ctx, g_out, g_ld):
         Lc, Sc, Uc, P, out = ctx.saved_tensors
         d, home = Sc.numel(), ctx.home
-        go = None if g_out is None else g_out.contiguous()
-        gl = None if g_ld is None else g_ld.contiguous()
+        go = _contig(g_out)
+        gl = _contig(g_ld)
         if home is not None:  # L, S, U back to back in a train.FlatParameters buffer: added to their gradient slice
             buf = home[0].grad[home[1]:home[1] + home[2]]
         else:
@@ -2284,9 +2168,8 @@ class Glow(_TwoWayFlow):
                 self._w_img[inverse] = None
             else:
                 if self._w_index is None or self._w_index.device != device:
-                    idx = (ctypes.c_int32 * n)()
-                    _lib.check("mnf_linear_rows_image_index", lib.mnf_linear_rows_image_index(self.dim, idx))
-                    self._w_index = torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
+                    self._w_index = _index_on(device, _counted_index(
+                        lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (self.dim,)))
                 img = torch.empty(n, dtype=torch.float32, device=device)
                 _lib.check("mnf_pack_gather", lib.mnf_pack_gather(
                     W.data_ptr(), self._w_index.data_ptr(), img.data_ptr(), n, _stream()))
@@ -2377,9 +2260,8 @@ class _SplineBlockRun:
                 A, b = torch.exp(s)[:, None] * W, t @ W
                 ldc = s.sum() + gl._w_ld
             if self._lin_index is None or self._lin_index.device != device:
-                idx = (ctypes.c_int32 * n)()
-                _lib.check("mnf_linear_rows_image_index", lib.mnf_linear_rows_image_index(self.dim, idx))
-                self._lin_index = torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
+                self._lin_index = _index_on(device, _counted_index(
+                    lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (self.dim,)))
             aff = torch.empty(n + self.dim, dtype=torch.float32, device=device)
             _lib.check("mnf_pack_gather", lib.mnf_pack_gather(
                 A.contiguous().data_ptr(), self._lin_index.data_ptr(), aff.data_ptr(), n, _stream()))
