@@ -25,7 +25,6 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_rt_bwd.h"
 
 namespace mnf {
@@ -45,7 +44,7 @@ struct AhfBwdRtArgs {
   int cb, bt, block_words, bias_words;  // weight stream (mnf_rt.h Source<false>)
   int ht_tiles, dt_tiles, ct_tiles;     // exchange tiles: hidden vectors of one net | one layer's deltas | a chunk
   NetDesc s_net, t_net;
-  int64_t slot_floats;  // 0; mnf_affine_half_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
+  int64_t slot_floats;  // 0; mnf_affine_half_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_rt_host.h)
   // a run of layers (n_layers = 1, outs = work = NULL: the one layer above)
   const float* outs;  // (n_layers, rows, dim): every applied layer's output; layer i reads x or outs[i - 1], and y = outs[i]
   float* work;        // (rows, dim): the cotangent plane that alternates with grad_x
@@ -283,16 +282,11 @@ static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_sc
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   sizes[n_hidden + 1] = H;
   if (w.min < 4 || w.max > (wide ? 128 : 64) || (wide && w.max <= 64)) return false;
-  int64_t off = 0;
-  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
-  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
-  if (!has_scale) a.s_net = a.t_net;
-  if (!has_shift) a.t_net = a.s_net;
-  if (off >= (1ll << 31)) return false;
-  a.n_params = (int)off;
+  const int64_t n_params = ahf_layout(n_hidden, sizes, has_scale, has_shift, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   p.mt_max = wide ? 8 : 4;
   a.bt = 8;  // (a layer's bias tiles: at most 8 at 128 units)
-  a.bias_words = 2 * a.bt * 16;
   a.ht_tiles = w.tiles;
   a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
   const int KS1 = (16 * ((hidden[0] + 15) / 16) + 31) / 32;
@@ -303,57 +297,47 @@ static bool ahf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, int has_sc
   // 8 = 16 blocks at 128 hidden units (and a K-step of a 128-unit layer 8), so 24 or 16 blocks per buffer; four layers
   // of 128 units are 32 exchange tiles, which leave room for 32 rows (nw = 2) beside the 64 KB of weight stream.
   const int cb_lo = wide ? 16 : 8, cb_step = wide ? 8 : 4;
-  for (p.nw = wide ? MNF_AHF_BWD_RT_WIDE_THREADS / 64 : 8; p.nw >= 1; --p.nw) {
-    for (int cb = cb_lo + cb_step; cb >= cb_lo; cb -= cb_step) {
-      int ci = cb / KS1;
-      ci = ci > p.mt_max ? p.mt_max : ci < 2 ? 2 : ci;
-      for (int ct = ci; ct >= 2; ct = ct > 2 ? 2 : 0) {
-        p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)2 * cb * rt::kBlockWords * 4 + (size_t)a.bias_words * 4 +
-                rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, ct);
-        if (p.lds <= 160 * 1024) {
-          a.cb = cb;
-          a.block_words = 2 * cb * rt::kBlockWords;
-          a.ct_tiles = ct;
-          return true;
-        }
-      }
-    }
-  }
-  return false;
+  return rt::fit_bwd_lds(a, a, p, {/*nw_max=*/wide ? MNF_AHF_BWD_RT_WIDE_THREADS / 64 : 8, cb_lo + cb_step, cb_lo, cb_step, KS1,
+                                   /*ct_min=*/2, /*ct_max=*/p.mt_max});
 }
+
+// the plan with the shape bound; a slot holds the parameters of all n_layers layers (the frame: mnf_rt_host.h)
+struct ahf_bwd_rt_slots {
+  int dim, n_hidden;
+  const int* hidden;
+  int has_scale, has_shift;
+  bool wide;
+  int n_layers;
+  int64_t operator()(AhfBwdRtArgs& a, RtPlan& p) const {
+    if (n_layers < 1 || n_layers > 32 || !ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, wide, a, p)) return 0;
+    return (int64_t)n_layers * a.n_params;
+  }
+};
 
 }  // namespace mnf
 
 using namespace mnf;
 
 extern "C" int mnf_affine_half_bwd_rt_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
-  AhfBwdRtArgs a;
-  RtPlan p;
-  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, false, a, p) ? 1 : 0;
+  return rt_has_plan<AhfBwdRtArgs>(ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, false, 1});
 }
 
 // ... and the shapes of the wide instantiation: 1 exactly where the widest hidden layer has 65 .. 128 units and a plan
 // exists -- never where the query above answers 1
 extern "C" int mnf_affine_half_bwd_rt_wide_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
-  AhfBwdRtArgs a;
-  RtPlan p;
-  return ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+  return rt_has_plan<AhfBwdRtArgs>(ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, true, 1});
 }
 
 // Which runs go out as one launch: 1 .. 32 layers of a shape the kernel has (every shape class of the plan: the layer
 // loop adds one weight-maximum pass and three barriers per layer to what n launches do, and takes n - 1 launches away).
 extern "C" int mnf_affine_half_bwd_rt_stack_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                                       int n_layers) {
-  AhfBwdRtArgs a;
-  RtPlan p;
-  return n_layers >= 1 && n_layers <= 32 && ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, false, a, p) ? 1 : 0;
+  return rt_has_plan<AhfBwdRtArgs>(ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, false, n_layers});
 }
 
 extern "C" int mnf_affine_half_bwd_rt_wide_stack_supported(int dim, int n_hidden, const int* hidden, int has_scale,
                                                            int has_shift, int n_layers) {
-  AhfBwdRtArgs a;
-  RtPlan p;
-  return n_layers >= 1 && n_layers <= 32 && ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+  return rt_has_plan<AhfBwdRtArgs>(ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, true, n_layers});
 }
 
 // the plan's kernel, its dynamic-LDS attribute set
@@ -365,13 +349,8 @@ static void (*ahf_bwd_rt_kernel_of(const RtPlan& p))(AhfBwdRtArgs) {
 
 static int64_t ahf_bwd_rt_workspace(int64_t rows, int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                     int n_layers, bool wide) {
-  AhfBwdRtArgs a;
-  RtPlan p;
-  if (rows < 1 || rows * dim >= (1ll << 40) || n_layers < 1 || n_layers > 32 ||
-      !ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, wide, a, p))
-    return 0;
-  if (!gfx950_visible()) return 0;
-  return rt_det_workspace(ahf_bwd_rt_kernel_of(p), p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params);
+  return rt_det_workspace<AhfBwdRtArgs>(rows, dim, ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, wide, n_layers},
+                                        ahf_bwd_rt_kernel_of);
 }
 
 extern "C" int64_t mnf_affine_half_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden, int has_scale,
@@ -395,7 +374,7 @@ extern "C" int64_t mnf_affine_half_bwd_rt_wide_stack_det_workspace(int64_t rows,
 }
 
 // One layer (outs = work = NULL, n_layers = 1, y its output) or a run (y = NULL); lp: grad_ld is d loss / d log p.
-// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd); wide: the *_wide entries' shapes
+// det: fixed-order parameter sums through `workspace` (mnf_rt_host.h run_rt_bwd); wide: the *_wide entries' shapes
 static int ahf_bwd_rt_run(const float* x, const float* y, const float* outs, const float* grad_y, const float* grad_ld, int lp,
                           float* grad_x, float* work, float* grad_flat, const float* flat, const float* grad_scale_dev,
                           uint32_t parity_bits, int n_layers, int64_t rows, int dim, int inverse, int n_hidden,
@@ -403,23 +382,20 @@ static int ahf_bwd_rt_run(const float* x, const float* y, const float* outs, con
                           int64_t workspace_floats, void* stream) {
   if (!x || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
-  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
-  if (rows == 0) return MNF_OK;
-  if ((inverse && has_scale && !y && !outs) || (!det && deterministic()) || rows * dim >= (1ll << 40) ||
-      rows * dim * n_layers >= (1ll << 42))
-    return MNF_ERR_UNSUPPORTED;
-  AhfBwdRtArgs a;
-  memset(&a, 0, sizeof(a));
-  RtPlan p;
-  if (!ahf_bwd_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, wide, a, p)) return MNF_ERR_UNSUPPORTED;
-  a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
-  a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity_bits; a.inverse = inverse != 0;
-  a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
-  a.outs = outs; a.work = work; a.n_layers = n_layers; a.lp = lp;
-  // (the planes of outs are rows * dim floats apart: dim % 8 == 0 keeps them aligned with the base)
-  a.vec = dim % 8 == 0 && aligned16(x, grad_x, y, grad_y, outs, work);
-  return launch_rt_bwd(ahf_bwd_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)16 * p.nw, rows, (int64_t)n_layers * a.n_params, det,
-                       workspace, workspace_floats, n_layers > 1 ? "ahf_bwd_stack_rt" : "ahf_bwd_rt", (hipStream_t)stream);
+  auto fill = [&](AhfBwdRtArgs& a) {
+    a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
+    a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity_bits; a.inverse = inverse != 0;
+    a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
+    a.outs = outs; a.work = work; a.n_layers = n_layers; a.lp = lp;
+    // (the planes of outs are rows * dim floats apart: dim % 8 == 0 keeps them aligned with the base)
+    a.vec = dim % 8 == 0 && aligned16(x, grad_x, y, grad_y, outs, work);
+  };
+  // (the inverse's scale gradient needs the layer's output; a run's planes stay below 2^42 elements)
+  const bool unsupported = (inverse && has_scale && !y && !outs) || rows * dim * n_layers >= (1ll << 42);
+  return run_rt_bwd<AhfBwdRtArgs>(
+      {rows, dim, grad_flat, det, workspace, workspace_floats, n_layers > 1 ? "ahf_bwd_stack_rt" : "ahf_bwd_rt", stream},
+      /*in_domain=*/true, unsupported, ahf_bwd_rt_slots{dim, n_hidden, hidden, has_scale, has_shift, wide, n_layers}, fill,
+      ahf_bwd_rt_kernel_of);
 }
 
 extern "C" int mnf_affine_half_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,

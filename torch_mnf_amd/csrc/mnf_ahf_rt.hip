@@ -20,8 +20,7 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
-#include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 
@@ -285,50 +284,37 @@ static bool ahf_rt_plan(int dim, int n_hidden, const int* hidden, int has_scale,
   sizes[n_hidden + 1] = H;
   // (widths < 4: a sum of one or two split products is not a 1e-5 sum, flows.py _MIN_SPLIT_HIDDEN)
   if (w.min < 4 || w.max > 256) return false;
-  int64_t off = 0;
-  if (has_scale) off += fill_net(a.s_net, n_hidden + 2, sizes, off);
-  if (has_shift) off += fill_net(a.t_net, n_hidden + 2, sizes, off);
-  if (!has_scale) a.s_net = a.t_net;
-  if (!has_shift) a.t_net = a.s_net;
-  if (off >= (1ll << 31)) return false;
-  a.n_params = (int)off;
+  const int64_t n_params = ahf_layout(n_hidden, sizes, has_scale, has_shift, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   a.vec = dim % 8 == 0 && aligned;
-  // blocks and bias tiles of the whole conditioner (the resident image)
+  // blocks and bias tiles of the whole conditioner (the resident image): every layer of each net there is
   const int heads = (has_scale ? 1 : 0) + (has_shift ? 1 : 0);
-  int64_t n_blocks = 0, n_bias = 0;
-  for (int l = 0; l <= n_hidden; ++l) {
-    const int in_cols = l == 0 ? H : 16 * ((sizes[l] + 15) / 16);
-    const int KS = (in_cols + 31) / 32, MT = (sizes[l + 1] + 15) / 16;
-    n_blocks += (int64_t)heads * KS * MT;
-    n_bias += (int64_t)heads * MT;
-  }
+  StagedTiles image = mlp_tiles(sizes, n_hidden + 1, H);
+  image.blocks *= heads;
+  image.bias *= heads;
   // Rows that are not 16-byte aligned (dim not a multiple of 8, a view at an odd offset) have the resident variant only,
   // except in the widest class, whose streaming kernel takes the alignment at run time (a branch around every row access:
   // 15-20 % on the memory-bound shapes) and serves every width: such a call goes there.
-  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
-  p.resident = n_blocks * 2048 + n_bias * 64 <= 158 * 1024;
-  p.mt_max = !p.resident && !a.vec ? 16 : w.max <= 64 ? 4 : w.max <= 128 ? 8 : 16;
-  a.cb = p.resident ? (int)n_blocks : kStream;
-  a.bt = p.resident ? (int)n_bias : kStream;
-  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
-  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
-  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
-  // workgroups of 8 waves (4 in the widest class) -- of 4 when the LDS footprint lets a CU hold two or more of them (they
-  // overlap each other's barriers, staging and memory waits; streaming: every wave of the CU shares one conversion of the
-  // weights)
-  p.nw = p.mt_max == 16 || (p.resident && p.lds <= 79 * 1024) ? 4 : 8;
+  plan_staging(a, p, image, /*resident_bytes=*/158 * 1024, /*stream=*/16);
+  p.mt_max = !p.resident && !a.vec ? 16 : rt_size_class(w.max);
+  p.nw = rt_fwd_waves(p);
   return true;
 }
 
+// the plan's kernel (vec: the arguments' a.vec), its dynamic-LDS attribute set
 template <int MT_MAX, int NW>
-static int ahf_rt_launch_class(const AhfRtArgs& a, const RtPlan& p, hipStream_t stream) {
+static void (*ahf_rt_kernel_class(const RtPlan& p, bool vec))(AhfRtArgs) {
   constexpr int kStreamVec = MT_MAX == 16 ? 2 : 1;
   static DeviceMemo attr;
   allow_big_lds(attr, ahf_rt_kernel<MT_MAX, 1, NW, true, 1>, ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>,
                 ahf_rt_kernel<MT_MAX, 1, NW, true, 0>);
-  auto kernel = !p.resident ? ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>
-                            : a.vec ? ahf_rt_kernel<MT_MAX, 1, NW, true, 1> : ahf_rt_kernel<MT_MAX, 1, NW, true, 0>;
-  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, a.n_layers > 1 ? "ahf_stack_rt" : "ahf_rt", stream);
+  return !p.resident ? ahf_rt_kernel<MT_MAX, 1, NW, false, kStreamVec>
+                     : vec ? ahf_rt_kernel<MT_MAX, 1, NW, true, 1> : ahf_rt_kernel<MT_MAX, 1, NW, true, 0>;
+}
+static void (*ahf_rt_kernel_of(const RtPlan& p, bool vec))(AhfRtArgs) {
+  return p.mt_max == 4 ? ahf_rt_kernel_class<4, 8>(p, vec)
+                       : p.mt_max == 8 ? ahf_rt_kernel_class<8, 8>(p, vec) : ahf_rt_kernel_class<16, 4>(p, vec);
 }
 
 // Which runs go out as one launch: 1 .. 32 layers of a shape the kernel has.  Measured out: runs of the widest class's
@@ -357,9 +343,7 @@ int ahf_rt_stack_launch(const float* x, float* y, float* mid, float* log_det, fl
   a.lp_sum = lp_sum; a.flat = flats; a.rows = rows; a.dim = dim; a.parity = parity_bits; a.n_layers = n_layers;
   a.inverse = inverse != 0; a.accumulate = accumulate != 0;
   a.has_scale = has_scale != 0; a.has_shift = has_shift != 0;
-  if (p.mt_max == 4) return ahf_rt_launch_class<4, 8>(a, p, stream);
-  if (p.mt_max == 8) return ahf_rt_launch_class<8, 8>(a, p, stream);
-  return ahf_rt_launch_class<16, 4>(a, p, stream);
+  return launch_plan(ahf_rt_kernel_of(p, a.vec != 0), a, p, 1, rows, n_layers > 1 ? "ahf_stack_rt" : "ahf_rt", stream);
 }
 
 // one layer; MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
@@ -373,9 +357,9 @@ int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accu
 }  // namespace mnf
 
 extern "C" int mnf_affine_half_rt_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
-  mnf::AhfRtArgs a;
-  mnf::RtPlan p;
-  return mnf::ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p) ? 1 : 0;
+  return mnf::rt_has_plan<mnf::AhfRtArgs>([&](mnf::AhfRtArgs& a, mnf::RtPlan& p) {
+    return mnf::ahf_rt_plan(dim, n_hidden, hidden, has_scale, has_shift, true, a, p);
+  });
 }
 
 extern "C" int mnf_affine_half_rt_stack_supported(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,

@@ -99,67 +99,10 @@ inline int64_t balanced_grid(int64_t n_tiles, int waves_per_block, int resident_
   return best;
 }
 
-// The run-time-shaped matrix-core kernels (mnf_rt.h: any layer count and widths, weights from `flat`) take a call from this
-// many rows on; below, the VALU any-shape kernels of mnf_generic.hip (one workgroup per few rows) have the lower latency.
+// The run-time-shaped matrix-core launchers (mnf_*_rt.hip, mnf_rt.h: any layer count and widths, weights from `flat`; the
+// host side they share: mnf_rt_host.h).  The dispatchers of mnf_generic.hip hand them a call from kRtMinRows rows on; below,
+// the VALU any-shape kernels (one workgroup per few rows) have the lower latency.
 constexpr int64_t kRtMinRows = 2048;
-
-// Host side of their launchers (mnf_*_rt.hip).  Each has a plan function of the shape alone -- false where the kernel has
-// no launch for the shape, else the kernel arguments' shape part and an RtPlan -- which its mnf_*_rt_supported query
-// answers from too.
-struct RtPlan {
-  int mt_max;     // size class: hidden tiles of a vector (4 / 8 / 16: widths up to 64 / 128 / 256)
-  bool resident;  // forward kernels: the whole conditioner staged into LDS once (else chunk by chunk)
-  int nw;         // waves per workgroup
-  size_t lds;     // dynamic LDS bytes
-};
-// sizes[1 .. n_hidden] := hidden[]; the smallest and largest width and the 16-unit tiles of all of them
-struct HiddenWidths {
-  int min, max, tiles;
-};
-inline HiddenWidths scan_hidden(int n_hidden, const int* hidden, int* sizes) {
-  HiddenWidths w{1 << 30, 0, 0};
-  for (int i = 0; i < n_hidden; ++i) {
-    sizes[1 + i] = hidden[i];
-    w.min = hidden[i] < w.min ? hidden[i] : w.min;
-    w.max = hidden[i] > w.max ? hidden[i] : w.max;
-    w.tiles += (hidden[i] + 15) / 16;
-  }
-  return w;
-}
-// every pointer 16-byte aligned (a null one is): the kernels' dwordx4 row accesses
-template <typename... P>
-inline bool aligned16(const P*... p) {
-  return (((reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
-}
-// up to 160 KB of dynamic LDS for each of `kernels`, set once per device (`memo`: the call site's own)
-template <typename... K>
-inline void allow_big_lds(DeviceMemo& memo, K... kernels) {
-  memo.get([&](int) {
-    ((void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024),
-     ...);
-    return 1;
-  });
-}
-// persistent grid: as many workgroups of nw waves as the occupancy query says are resident (one per CU if it fails), at
-// most one per `rows_per_block` rows
-template <typename Args>
-inline int64_t persistent_grid(void (*kernel)(Args), int nw, size_t lds, int64_t rows_per_block, int64_t rows) {
-  int per_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, nw * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  const int64_t need = (rows + rows_per_block - 1) / rows_per_block;
-  const int64_t grid = (int64_t)per_cu * device_cus(current_device());
-  return grid > need ? need : grid;
-}
-// ... launched; tags the launch with the kernel family `tag`
-template <typename Args>
-inline int launch_persistent(void (*kernel)(Args), const Args& a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
-                             const char* tag, hipStream_t stream) {
-  const int64_t grid = persistent_grid(kernel, nw, lds, rows_per_block, rows);
-  tag_kernel(tag);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(nw * 64), lds, stream, a);
-  return check_launch();
-}
-
 int ahf_rt_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const float* flat, int64_t rows,
                   int dim, int parity, int inverse, int n_hidden, const int* hidden, int has_scale, int has_shift,
                   hipStream_t stream);
@@ -223,47 +166,8 @@ bool deterministic();
 // n floats := 0 / dst[i] += part[0][i] + part[1][i] + ... (rows in order, row r at part + r * stride), as kernel nodes
 int zero_floats_async(float* p, int64_t n, hipStream_t stream);
 int det_reduce_async(const float* part, int n_rows, int64_t stride, int64_t count, float* dst, hipStream_t stream);
-
-// The fixed-order form of the run-time-shaped gradient launches (mnf_*_bwd_rt_det): every workgroup of the persistent
-// grid adds into a slot of its own (grad_flat + blockIdx.x * slot_floats), and det_reduce_async adds the slots up in
-// order.  A parameter's entry in a slot receives its adds from ONE lane, in program order (the weight-gradient products
-// go to the waves by shape alone, mnf_rt_bwd.h dw_phase_rows), so that every slot -- and the sum -- is the same every
-// run.  The grid is persistent_grid's, capped so that the slots stay within kRtDetMaxBytes.
-constexpr int64_t kRtDetMaxBytes = (int64_t)512 << 20;
-inline int64_t rt_det_slot_floats(int64_t n_params) { return (n_params + 63) / 64 * 64; }  // whole 256-byte lines
-inline int64_t rt_det_slots(int64_t grid, int64_t n_params) {
-  int64_t cap = kRtDetMaxBytes / (4 * rt_det_slot_floats(n_params));
-  if (cap < 1) cap = 1;
-  return grid < cap ? grid : cap;
-}
 bool gfx950_visible();  // mnf_device_count() > 0, asked once per process
-// det: the slots in `workspace` (at least slots x slot_floats floats, else MNF_ERR_INVALID_ARG before any launch), zeroed,
-// filled, added to a.grad_flat; grad_flat == NULL or !det: launch_persistent
-template <typename Args>
-inline int launch_rt_bwd(void (*kernel)(Args), Args a, int nw, size_t lds, int64_t rows_per_block, int64_t rows,
-                         int64_t n_params, bool det, float* workspace, int64_t workspace_floats, const char* tag,
-                         hipStream_t stream) {
-  a.slot_floats = 0;
-  if (!det || !a.grad_flat) return launch_persistent(kernel, a, nw, lds, rows_per_block, rows, tag, stream);
-  const int64_t slots = rt_det_slots(persistent_grid(kernel, nw, lds, rows_per_block, rows), n_params);
-  const int64_t slot = rt_det_slot_floats(n_params);
-  if (!workspace || workspace_floats < slots * slot) return MNF_ERR_INVALID_ARG;
-  float* const dst = a.grad_flat;
-  a.grad_flat = workspace;
-  a.slot_floats = slot;
-  int rc = zero_floats_async(workspace, slots * slot, stream);
-  if (rc != MNF_OK) return rc;
-  tag_kernel(tag);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)slots), dim3(nw * 64), lds, stream, a);
-  rc = check_launch();
-  return rc != MNF_OK ? rc : det_reduce_async(workspace, (int)slots, slot, n_params, dst, stream);
-}
-// floats of workspace launch_rt_bwd's det form needs (0: no gfx950 device visible)
-template <typename K>
-inline int64_t rt_det_workspace(K kernel, int nw, size_t lds, int64_t rows_per_block, int64_t rows, int64_t n_params) {
-  if (rows < 1 || !gfx950_visible()) return 0;
-  return rt_det_slots(persistent_grid(kernel, nw, lds, rows_per_block, rows), n_params) * rt_det_slot_floats(n_params);
-}
+
 // The fp32 fix-up passes under MNF_DETERMINISTIC: the matrix-core gradient launches hand back the tiles / row groups
 // whose operands left the split range as a LIST filled through an atomic counter -- the same ids every run, in any order.
 // det_sort_ids_async sorts ids[0 .. min(*count, capacity)) (distinct values in [0, n_items)) ascending, in place, as a

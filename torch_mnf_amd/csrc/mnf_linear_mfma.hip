@@ -10,7 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include "mnf_device.h"
-#include "mnf_host.h"
+#include "mnf_rt_host.h"  // (the Glow kernels at any dim launch like the run-time-shaped ones)
 
 namespace mnf {
 

@@ -15,7 +15,6 @@
 #include <cstring>
 
 #include "../../include/mnf_hip.h"
-#include "mnf_host.h"
 #include "mnf_rnvp_common.h"
 #include "mnf_rt_bwd.h"
 
@@ -37,7 +36,7 @@ struct MafBwdRtArgs {
   int ht_tiles, dt_tiles, ct_tiles;
   int m_off[MNF_MAX_LINEAR];  // byte offset of layer l's mask
   NetDesc net;                // dim -> h_1 .. h_n
-  int64_t slot_floats;        // 0; mnf_maf_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
+  int64_t slot_floats;        // 0; mnf_maf_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_rt_host.h)
 };
 
 // columns col .. col + 3 of a row seen flipped (column c <-> d-1-c): zeros beyond d; vec: one dwordx4 (d % 4 == 0).  No load
@@ -216,46 +215,18 @@ static bool maf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, MafBwdRtAr
   sizes[0] = dim;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   if (w.min < 4 || w.max > 64) return false;  // the one size class built (4 hidden tiles)
-  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0), moff = 0;
-  const int hl = hidden[n_hidden - 1];
-  for (int l = 0; l < n_hidden; ++l) {
-    a.m_off[l] = (int)moff;
-    moff += (int64_t)sizes[l] * sizes[l + 1];
-  }
-  a.m_off[n_hidden] = (int)moff;
-  moff += 2ll * dim * hl;
-  a.s_w = (int)off; off += 2ll * dim * hl;
-  a.s_b = (int)off; off += 2ll * dim;
-  if (off >= (1ll << 31) || moff >= (1ll << 31)) return false;
-  a.n_params = (int)off;
+  const int64_t n_params = maf_layout(dim, n_hidden, sizes, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   p.mt_max = 4;
   p.resident = false;
-  const int MTh = (hl + 15) / 16, KSh = (16 * MTh + 31) / 32;
-  a.cb = 4 * KSh > 2 * MTh ? 4 * KSh : 2 * MTh;  // a round of the last layer: 2 tiles x 2 heads x KSh blocks, then 2 x MTh turned ones
-  const int MT1 = (hidden[0] + 15) / 16;
-  if (a.cb < MT1) a.cb = MT1;  // (a K-step of the first layer)
-  if (a.cb < 8) a.cb = 8;
+  a.cb = rt::bwd_head_round_blocks(hidden[n_hidden - 1], hidden[0]);  // (the heads: the last MaskedLinear's s and t)
   a.bt = 4;
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
   a.ht_tiles = w.tiles;
   a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
-  // rows per workgroup first (any wave count), then as many first-layer input tiles per chunk as still fit (the
-  // output-layer chunks need four: [s0 s1 t0 t1])
-  const int KS1 = (16 * MT1 + 31) / 32;
-  int ci = a.cb / KS1;
-  ci = ci > p.mt_max ? p.mt_max : ci < 4 ? 4 : ci;
-  for (p.nw = 8; p.nw >= 1; --p.nw) {
-    for (int ct = ci; ct >= 4; ct = ct > 4 ? 4 : 0) {
-      p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
-              rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, ct);
-      if (p.lds <= 160 * 1024) {
-        a.ct_tiles = ct;
-        return true;
-      }
-    }
-  }
-  return false;
+  // (the output-layer chunks need four tiles: [s0 s1 t0 t1])
+  const int KS1 = (16 * ((hidden[0] + 15) / 16) + 31) / 32;
+  return rt::fit_bwd_lds(a, a, p, {/*nw_max=*/8, a.cb, a.cb, 1, KS1, /*ct_min=*/4, /*ct_max=*/p.mt_max});
 }
 
 }  // namespace mnf
@@ -263,9 +234,7 @@ static bool maf_bwd_rt_plan(int dim, int n_hidden, const int* hidden, MafBwdRtAr
 using namespace mnf;
 
 extern "C" int mnf_maf_bwd_rt_supported(int dim, int n_hidden, const int* hidden) {
-  MafBwdRtArgs a;
-  RtPlan p;
-  return maf_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<MafBwdRtArgs>([&](MafBwdRtArgs& a, RtPlan& p) { return maf_bwd_rt_plan(dim, n_hidden, hidden, a, p); });
 }
 
 // the plan's kernel, its dynamic-LDS attribute set
@@ -276,31 +245,27 @@ static void (*maf_bwd_rt_kernel_of(const RtPlan&))(MafBwdRtArgs) {
 }
 
 extern "C" int64_t mnf_maf_bwd_rt_det_workspace(int64_t rows, int dim, int n_hidden, const int* hidden) {
-  MafBwdRtArgs a;
-  RtPlan p;
-  if (rows < 1 || rows * dim >= (1ll << 40) || !maf_bwd_rt_plan(dim, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return rt_det_workspace(maf_bwd_rt_kernel_of(p), p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params);
+  return rt_det_workspace<MafBwdRtArgs>(
+      rows, dim, [&](MafBwdRtArgs& a, RtPlan& p) { return maf_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? a.n_params : 0; },
+      maf_bwd_rt_kernel_of);
 }
 
-// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+// det: fixed-order parameter sums through `workspace` (mnf_rt_host.h run_rt_bwd)
 static int maf_bwd_rt_run(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
                           const float* flat, const uint8_t* masks, const float* grad_scale_dev, int64_t rows, int dim, int parity,
                           int n_hidden, const int* hidden, bool det, float* workspace, int64_t workspace_floats, void* stream) {
   if (!x || !grad_x || x == grad_x || !flat || !masks || !grad_scale_dev || rows < 0 || dim < 1 || n_hidden < 1 ||
       !hidden_ok(n_hidden, hidden) || (grad_y && grad_y == grad_x) || (grad_flat && grad_flat == flat))
     return MNF_ERR_INVALID_ARG;
-  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
-  if (rows == 0) return MNF_OK;
-  if ((!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
-  MafBwdRtArgs a;
-  memset(&a, 0, sizeof(a));
-  RtPlan p;
-  if (!maf_bwd_rt_plan(dim, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
-  a.x = x; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat; a.masks = masks;
-  a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity != 0;
-  a.vec = dim % 4 == 0 && aligned16(x, grad_x, grad_y);
-  return launch_rt_bwd(maf_bwd_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params, det, workspace,
-                       workspace_floats, "maf_bwd_rt", (hipStream_t)stream);
+  auto fill = [&](MafBwdRtArgs& a) {
+    a.x = x; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat; a.masks = masks;
+    a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity != 0;
+    a.vec = dim % 4 == 0 && aligned16(x, grad_x, grad_y);
+  };
+  return run_rt_bwd<MafBwdRtArgs>(
+      {rows, dim, grad_flat, det, workspace, workspace_floats, "maf_bwd_rt", stream}, /*in_domain=*/true, /*unsupported=*/false,
+      [&](MafBwdRtArgs& a, RtPlan& p) { return maf_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? a.n_params : 0; }, fill,
+      maf_bwd_rt_kernel_of);
 }
 
 extern "C" int mnf_maf_bwd_rt(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,

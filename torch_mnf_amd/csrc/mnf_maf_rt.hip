@@ -16,9 +16,8 @@
 #include <cstring>
 
 #include "../../include/mnf_hip.h"
-#include "mnf_host.h"
 #include "mnf_rnvp_common.h"
-#include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 
@@ -144,39 +143,19 @@ static bool maf_rt_plan(int dim, int n_hidden, const int* hidden, MafRtArgs& a, 
   sizes[0] = dim;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   if (w.min < 4 || w.max > 16 * kMafRtClass) return false;
-  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0), moff = 0;
-  const int hl = hidden[n_hidden - 1];
-  for (int l = 0; l < n_hidden; ++l) {
-    a.m_off[l] = (int)moff;
-    moff += (int64_t)sizes[l] * sizes[l + 1];
-  }
-  a.m_off[n_hidden] = (int)moff;
-  moff += 2ll * dim * hl;
-  a.s_w = (int)off; off += 2ll * dim * hl;
-  a.s_b = (int)off; off += 2ll * dim;
-  if (off >= (1ll << 31) || moff >= (1ll << 31)) return false;
-  a.n_params = (int)off;
-  int64_t n_blocks = 0, n_bias = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    const int in_cols = l == 0 ? dim : 16 * ((sizes[l] + 15) / 16);
-    n_blocks += (int64_t)((in_cols + 31) / 32) * ((sizes[l + 1] + 15) / 16);
-    n_bias += (sizes[l + 1] + 15) / 16;
-  }
-  const int KS = (16 * ((hl + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
-  n_blocks += 2ll * KS * M;
-  n_bias += 2ll * M;
-  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
-  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
+  const int64_t n_params = maf_layout(dim, n_hidden, sizes, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
+  // the resident image: the net, then the last MaskedLinear's s and t tiles
+  StagedTiles image = mlp_tiles(sizes, n_hidden, dim);
+  const int KS = (16 * ((hidden[n_hidden - 1] + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
+  image.blocks += 2ll * KS * M;
+  image.bias += 2ll * M;
+  plan_staging(a, p, image, /*resident_bytes=*/150 * 1024, /*stream=*/16);
   p.mt_max = kMafRtClass;
-  a.cb = p.resident ? (int)n_blocks : kStream;
-  a.bt = p.resident ? (int)n_bias : kStream;
-  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
-  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
-  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
   p.nw = kMafRtWaves;
   return true;
 }
-
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The element-by-element direction (MAF.forward, IAF.inverse: flows/maf.py:39-51), family maf_seq_rt: per 16-row tile, for
@@ -316,8 +295,7 @@ __global__ void __launch_bounds__(kMafRtWaves * 64) maf_seq_rt_kernel(MafRtArgs 
 static bool maf_seq_rt_plan(int dim, int n_hidden, const int* hidden, MafRtArgs& a, RtPlan& p) {
   if (!maf_rt_plan(dim, n_hidden, hidden, a, p) || !p.resident) return false;
   const size_t slab = (size_t)256 * ((dim + 3) / 4);
-  int nw = kMafRtWaves;
-  while (nw >= 1 && p.lds + nw * slab > 160 * 1024) nw >>= 1;
+  const int nw = fit_slab_waves(kMafRtWaves, p.lds, slab);
   if (nw < 1) return false;
   p.nw = nw;
   p.lds += nw * slab;
@@ -329,9 +307,7 @@ static bool maf_seq_rt_plan(int dim, int n_hidden, const int* hidden, MafRtArgs&
 using namespace mnf;
 
 extern "C" int mnf_maf_rt_supported(int dim, int n_hidden, const int* hidden) {
-  MafRtArgs a;
-  RtPlan p;
-  return maf_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<MafRtArgs>([&](MafRtArgs& a, RtPlan& p) { return maf_rt_plan(dim, n_hidden, hidden, a, p); });
 }
 
 static void (*maf_rt_kernel_of(const RtPlan& p))(MafRtArgs) {
@@ -342,10 +318,8 @@ static void (*maf_rt_kernel_of(const RtPlan& p))(MafRtArgs) {
 
 // workgroups of the launch (each walks the row blocks of 16 x 8 rows blockIdx.x, + grid, ...); 0: no launch, or no device
 extern "C" int64_t mnf_maf_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden) {
-  MafRtArgs a;
-  RtPlan p;
-  if (rows < 1 || !maf_rt_plan(dim, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return persistent_grid(maf_rt_kernel_of(p), p.nw, p.lds, (int64_t)p.nw * 16, rows);
+  return rt_grid_query<MafRtArgs>(
+      rows, 1, [&](MafRtArgs& a, RtPlan& p) { return maf_rt_plan(dim, n_hidden, hidden, a, p); }, maf_rt_kernel_of);
 }
 
 extern "C" int mnf_maf_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
@@ -362,27 +336,23 @@ extern "C" int mnf_maf_rt(const float* x, float* y, float* log_det, int accumula
   a.parity = parity != 0;
   a.accumulate = accumulate != 0;
   a.vec = dim % 4 == 0 && aligned16(x, y);
-  return launch_persistent(maf_rt_kernel_of(p), a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "maf_rt", (hipStream_t)stream);
+  return launch_plan(maf_rt_kernel_of(p), a, p, 1, rows, "maf_rt", (hipStream_t)stream);
 }
 
-static void (*maf_seq_rt_kernel_of())(MafRtArgs) {
+static void (*maf_seq_rt_kernel_of(const RtPlan&))(MafRtArgs) {
   static DeviceMemo attr;
   allow_big_lds(attr, maf_seq_rt_kernel);
   return maf_seq_rt_kernel;
 }
 
 extern "C" int mnf_maf_seq_rt_supported(int dim, int n_hidden, const int* hidden) {
-  MafRtArgs a;
-  RtPlan p;
-  return maf_seq_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<MafRtArgs>([&](MafRtArgs& a, RtPlan& p) { return maf_seq_rt_plan(dim, n_hidden, hidden, a, p); });
 }
 
 // workgroups of the launch (each walks the row blocks of 16 x waves rows blockIdx.x, + grid, ...); 0: no launch, or no device
 extern "C" int64_t mnf_maf_seq_rt_grid(int64_t rows, int dim, int n_hidden, const int* hidden) {
-  MafRtArgs a;
-  RtPlan p;
-  if (rows < 1 || !maf_seq_rt_plan(dim, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return persistent_grid(maf_seq_rt_kernel_of(), p.nw, p.lds, (int64_t)p.nw * 16, rows);
+  return rt_grid_query<MafRtArgs>(
+      rows, 1, [&](MafRtArgs& a, RtPlan& p) { return maf_seq_rt_plan(dim, n_hidden, hidden, a, p); }, maf_seq_rt_kernel_of);
 }
 
 extern "C" int mnf_maf_seq_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, const uint8_t* masks,
@@ -399,5 +369,5 @@ extern "C" int mnf_maf_seq_rt(const float* x, float* y, float* log_det, int accu
   a.parity = parity != 0;
   a.accumulate = accumulate != 0;
   a.vec = dim % 4 == 0 && aligned16(x, y);
-  return launch_persistent(maf_seq_rt_kernel_of(), a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "maf_seq_rt", (hipStream_t)stream);
+  return launch_plan(maf_seq_rt_kernel_of(p), a, p, 1, rows, "maf_seq_rt", (hipStream_t)stream);
 }

@@ -21,7 +21,6 @@
 #include <cstring>
 
 #include "../../include/mnf_hip.h"
-#include "mnf_host.h"
 #include "mnf_rnvp_common.h"
 #include "mnf_rt_bwd.h"
 
@@ -290,36 +289,22 @@ __global__ void __launch_bounds__(512) maf_seq_bwd_rt_kernel(MafSeqBwdArgs a) {
 // The launch of a shape, or false: mnf_maf_bwd takes it.  Fills the kernel arguments' shape part.  mnf_maf_bwd_rt's shapes
 // whose images fit 160 KB of LDS next to the slabs of 8 / 4 / 2 / 1 waves.
 static bool maf_seq_bwd_rt_plan(int dim, int n_hidden, const int* hidden, MafSeqBwdArgs& a, RtPlan& p) {
-  if (dim < 1 || n_hidden < 1 || n_hidden > rt::kMaxBwdLayers || !hidden_ok(n_hidden, hidden)) return false;
+  // The envelope is the weight pass's own -- mnf_maf_bwd_rt's: its query checks dim, the layer count, the widths (4 .. 64,
+  // kSeqBwdClass tiles) and the layout's 31-bit guards, so nothing here repeats them
+  static_assert(kSeqBwdClass == 4, "mnf_maf_bwd_rt's size class");
   if (!mnf_maf_bwd_rt_supported(dim, n_hidden, hidden)) return false;
   int sizes[MNF_MAX_LINEAR + 1];
   sizes[0] = dim;
-  const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
-  if (w.min < 4 || w.max > 16 * kSeqBwdClass) return false;
-  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0), moff = 0;
+  scan_hidden(n_hidden, hidden, sizes);
+  maf_layout(dim, n_hidden, sizes, a);
   const int hl = hidden[n_hidden - 1];
-  for (int l = 0; l < n_hidden; ++l) {
-    a.m_off[l] = (int)moff;
-    moff += (int64_t)sizes[l] * sizes[l + 1];
-  }
-  a.m_off[n_hidden] = (int)moff;
-  moff += 2ll * dim * hl;
-  a.s_w = (int)off; off += 2ll * dim * hl;
-  a.s_b = (int)off; off += 2ll * dim;
-  if (off >= (1ll << 31) || moff >= (1ll << 31)) return false;
   auto t16 = [](int n) { return (n + 15) / 16; };
   auto s32 = [](int n) { return (n + 31) / 32; };
   const int M = t16(dim), MTh = t16(hl);
-  int64_t fwd = 0, tiles = 0, turned = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    const int in_cols = l == 0 ? dim : 16 * t16(sizes[l]);
-    fwd += (int64_t)s32(in_cols) * t16(sizes[l + 1]);
-    tiles += t16(sizes[l + 1]);
-  }
-  fwd += (int64_t)M * s32(16 * MTh);
-  tiles += M;
+  const StagedTiles net = mlp_tiles(sizes, n_hidden, dim);
+  const int64_t fwd = net.blocks + (int64_t)M * s32(16 * MTh), tiles = net.bias + M;
   a.t_off[0] = (int)fwd;
-  turned = (int64_t)M * s32(16 * t16(sizes[1]));
+  int64_t turned = (int64_t)M * s32(16 * t16(sizes[1]));
   for (int l = 1; l < n_hidden; ++l) {
     a.t_off[l] = (int)(fwd + turned);
     turned += (int64_t)s32(16 * t16(sizes[l + 1])) * t16(sizes[l]);
@@ -350,12 +335,11 @@ static bool maf_seq_bwd_rt_plan(int dim, int n_hidden, const int* hidden, MafSeq
   a.hp = 16 * MTh;
   const int64_t fixed = 4ll * kSeqBwdHeadWords + (fwd + turned) * rt::kBlockWords * 4 + tiles * 64 + 2ll * dim * a.hp * 4;
   const int64_t slab = 2ll * 1024 * M;  // G and e^{-s}: 16 rows x 16 M columns of floats each
-  if (fixed > 160 * 1024) return false;
+  if (fixed > (int64_t)kRtLdsBytes) return false;
   a.fwd_blocks = (int)fwd;
   a.turned_blocks = (int)turned;
   a.bias_tiles = (int)tiles;
-  int nw = 8;
-  while (nw >= 1 && fixed + nw * slab > 160 * 1024) nw >>= 1;
+  const int nw = fit_slab_waves(8, (size_t)fixed, (size_t)slab);
   if (nw < 1) return false;
   p.mt_max = kSeqBwdClass;
   p.resident = true;
@@ -371,7 +355,8 @@ static int64_t seq_bwd_workspace(int64_t rows, int dim) {
   return 2 * round4(rows * dim) + round4(rows) + 4;
 }
 
-static void (*maf_seq_bwd_rt_kernel_of())(MafSeqBwdArgs) {
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*maf_seq_bwd_rt_kernel_of(const RtPlan&))(MafSeqBwdArgs) {
   static DeviceMemo attr;
   allow_big_lds(attr, maf_seq_bwd_rt_kernel);
   return maf_seq_bwd_rt_kernel;
@@ -401,8 +386,7 @@ static int maf_seq_bwd_rt_run(const float* y, const float* grad_y, const float* 
   a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.cot = cot; a.neg_ld = grad_ld ? neg_ld : nullptr;
   a.flat = flat; a.masks = masks; a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.parity = parity != 0;
   a.vec = dim % 4 == 0 && aligned16(y, grad_x, grad_y, cot);
-  int rc = launch_persistent(maf_seq_bwd_rt_kernel_of(), a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "maf_seq_bwd_rt",
-                             (hipStream_t)stream);
+  int rc = launch_plan(maf_seq_bwd_rt_kernel_of(p), a, p, 1, rows, "maf_seq_bwd_rt", (hipStream_t)stream);
   if (rc != MNF_OK || !grad_flat) return rc;
   // the parameter gradients: the one-pass direction's at x := y, grad_y := cot, grad_ld := -grad_ld, parity := 0
   rc = mnf_affine_half_grad_scale(cot, a.neg_ld, rows, dim, scale2, stream);
@@ -419,9 +403,7 @@ static int maf_seq_bwd_rt_run(const float* y, const float* grad_y, const float* 
 using namespace mnf;
 
 extern "C" int mnf_maf_seq_bwd_rt_supported(int dim, int n_hidden, const int* hidden) {
-  MafSeqBwdArgs a;
-  RtPlan p;
-  return maf_seq_bwd_rt_plan(dim, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<MafSeqBwdArgs>([&](MafSeqBwdArgs& a, RtPlan& p) { return maf_seq_bwd_rt_plan(dim, n_hidden, hidden, a, p); });
 }
 
 extern "C" int64_t mnf_maf_seq_bwd_rt_workspace(int64_t rows, int dim) { return seq_bwd_workspace(rows, dim); }

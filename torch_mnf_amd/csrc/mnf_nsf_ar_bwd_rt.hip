@@ -24,13 +24,12 @@
 // split-f16 range of the weight-gradient products; the rows of the delta chain are scaled up as well as down on top of it
 // (rt::split_rows_both), so that a row's grad_x does not depend on which batch it is in.  Loop order: row block outer, group inner -- a group's weights are staged again for every row block and
 // its dW added once per row block.  The parameter sums are float atomics, each entry of a workgroup's from
-// one lane in program order: with a slot per workgroup (mnf_nsf_ar_bwd_rt_det, mnf_host.h launch_rt_bwd) they repeat bit
+// one lane in program order: with a slot per workgroup (mnf_nsf_ar_bwd_rt_det, mnf_rt_host.h launch_rt_bwd) they repeat bit
 // for bit.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_nsf_ar_rt.h"
 #include "mnf_nsf_spline_grad.h"
 #include "mnf_rt_bwd.h"
@@ -51,7 +50,7 @@ struct NsfArBwdRtArgs {
   int gvec;                // grad_x's rows are 16-byte aligned
   int ht_tiles, ct_tiles;  // exchange tiles: the hidden vectors | a phase's cotangent / input tiles
   int64_t sample, stride;  // the cotangent scale's sample: rows 0, stride, 2 stride, ...
-  int64_t slot_floats;     // 0; mnf_nsf_ar_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
+  int64_t slot_floats;     // 0; mnf_nsf_ar_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_rt_host.h)
 };
 
 // first exchange tile of hidden vector H_i (i >= 1) of the side-by-side net
@@ -426,52 +425,51 @@ static bool nsf_ar_bwd_rt_plan(int dim, int K, int n_hidden, const int* hidden, 
   if (a.f.cb < 12) a.f.cb = 12;
   if (a.f.cb > kArStream) return false;
   a.f.bt = TV > 8 ? TV : 8;
-  a.f.block_words = 2 * a.f.cb * rt::kBlockWords;
-  a.f.bias_words = 2 * a.f.bt * 16;
   a.ht_tiles = 0;
   for (int l = 0; l < n_hidden; ++l) a.ht_tiles += t16(4 * hidden[l]);
-  a.ct_tiles = TV > 4 ? TV : 4;
   p.mt_max = 4;
   p.resident = false;
-  for (p.nw = 8; p.nw >= 1; --p.nw) {  // (any wave count: fewer rows per block where the exchange area of 8 waves does not fit)
-    p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.f.block_words * 4 + (size_t)a.f.bias_words * 4 +
-            rt::bwd_lds_bytes(p.nw, a.ht_tiles, 0, a.ct_tiles);
-    if (p.lds <= 160 * 1024) return true;
-  }
-  return false;
+  // (one chunk size; any wave count: fewer rows per block where the exchange area of 8 waves does not fit)
+  const int ct = TV > 4 ? TV : 4;
+  return rt::fit_bwd_lds(a.f, a, p, {/*nw_max=*/8, a.f.cb, a.f.cb, 1, /*ks1=*/1, /*ct_min=*/ct, /*ct_max=*/ct});
 }
 
-static void (*nsf_ar_bwd_rt_kernel_of())(NsfArBwdRtArgs) {
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*nsf_ar_bwd_rt_kernel_of(const RtPlan&))(NsfArBwdRtArgs) {
   static DeviceMemo attr;
   allow_big_lds(attr, nsf_ar_bwd_rt_kernel);
   return nsf_ar_bwd_rt_kernel;
 }
 
-// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+// the plan with the shape bound; a slot holds all of `flat`
+struct nsf_ar_bwd_rt_slots {
+  int dim, K, n_hidden;
+  const int* hidden;
+  int64_t operator()(NsfArBwdRtArgs& a, RtPlan& p) const {
+    return nsf_ar_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? mnf_nsf_ar_flat_floats(dim, K, n_hidden, hidden) : 0;
+  }
+};
+
+// det: fixed-order parameter sums through `workspace` (mnf_rt_host.h run_rt_bwd)
 static int nsf_ar_bwd_rt_run(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
                              const float* flat, int64_t rows, int dim, int K, float tail_bound, int n_hidden, const int* hidden,
                              bool det, float* workspace, int64_t workspace_floats, void* stream) {
   if (!x || !grad_x || x == grad_x || !flat || rows < 0 || dim < 1 || K < 1 || !(tail_bound > 0.f) || !hidden_ok(n_hidden, hidden) ||
       (grad_y && grad_y == grad_x) || (grad_flat && grad_flat == flat))
     return MNF_ERR_INVALID_ARG;
-  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
-  if (1e-3 * K > 1.0) return MNF_ERR_DOMAIN;  // spline_flow.py:90-93
-  if (rows == 0) return MNF_OK;
-  if ((!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
-  NsfArBwdRtArgs a;
-  memset(&a, 0, sizeof(a));
-  RtPlan p;
-  if (!nsf_ar_bwd_rt_plan(dim, K, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
-  a.f.x = x; a.f.flat = flat; a.f.rows = rows; a.f.T = tail_bound;
-  a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat;
-  a.f.vec = dim % 4 == 0 && aligned16(x);
-  a.gvec = dim % 4 == 0 && aligned16(grad_x);
-  a.sample = rows < 512 ? rows : 512;  // (mnf_affine_half_grad_scale's sample, at most 65,536 values)
-  if (a.sample * dim > 65536) a.sample = 65536 / dim;
-  a.stride = rows / a.sample;
-  return launch_rt_bwd(nsf_ar_bwd_rt_kernel_of(), a, p.nw, p.lds, (int64_t)16 * p.nw, rows,
-                       mnf_nsf_ar_flat_floats(dim, K, n_hidden, hidden), det, workspace, workspace_floats, "nsf_ar_bwd_rt",
-                       (hipStream_t)stream);
+  auto fill = [&](NsfArBwdRtArgs& a) {
+    a.f.x = x; a.f.flat = flat; a.f.rows = rows; a.f.T = tail_bound;
+    a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat;
+    a.f.vec = dim % 4 == 0 && aligned16(x);
+    a.gvec = dim % 4 == 0 && aligned16(grad_x);
+    a.sample = rows < 512 ? rows : 512;  // (mnf_affine_half_grad_scale's sample, at most 65,536 values)
+    if (a.sample * dim > 65536) a.sample = 65536 / dim;
+    a.stride = rows / a.sample;
+  };
+  return run_rt_bwd<NsfArBwdRtArgs>(
+      {rows, dim, grad_flat, det, workspace, workspace_floats, "nsf_ar_bwd_rt", stream},
+      /*in_domain=*/1e-3 * K <= 1.0 /* spline_flow.py:90-93 */, /*unsupported=*/false, nsf_ar_bwd_rt_slots{dim, K, n_hidden, hidden},
+      fill, nsf_ar_bwd_rt_kernel_of);
 }
 
 }  // namespace mnf
@@ -479,17 +477,11 @@ static int nsf_ar_bwd_rt_run(const float* x, const float* grad_y, const float* g
 using namespace mnf;
 
 extern "C" int mnf_nsf_ar_bwd_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
-  NsfArBwdRtArgs a;
-  RtPlan p;
-  return nsf_ar_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<NsfArBwdRtArgs>(nsf_ar_bwd_rt_slots{dim, K, n_hidden, hidden});
 }
 
 extern "C" int64_t mnf_nsf_ar_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
-  NsfArBwdRtArgs a;
-  RtPlan p;
-  if (rows < 1 || rows * dim >= (1ll << 40) || !nsf_ar_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return rt_det_workspace(nsf_ar_bwd_rt_kernel_of(), p.nw, p.lds, (int64_t)16 * p.nw, rows,
-                          mnf_nsf_ar_flat_floats(dim, K, n_hidden, hidden));
+  return rt_det_workspace<NsfArBwdRtArgs>(rows, dim, nsf_ar_bwd_rt_slots{dim, K, n_hidden, hidden}, nsf_ar_bwd_rt_kernel_of);
 }
 
 extern "C" int mnf_nsf_ar_bwd_rt(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,

@@ -4,8 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "mnf_host.h"
-#include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 

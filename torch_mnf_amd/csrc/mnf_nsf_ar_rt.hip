@@ -23,10 +23,8 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_nsf_ar_rt.h"
 #include "mnf_nsf_spline.h"
-#include "mnf_rt.h"
 
 #ifndef MNF_NSF_AR_TILES
 #define MNF_NSF_AR_TILES 2  // row tiles per wave (profiles/r17/README.md)
@@ -154,17 +152,13 @@ static bool nsf_ar_rt_plan(int dim, int K, int n_hidden, const int* hidden, NsfA
   ArLayout& L = a.L;
   if (!ar_layout_plan(dim, K, n_hidden, hidden, L)) return false;
   p.mt_max = 4;
-  p.resident = false;
-  a.cb = kArStream;
-  a.bt = kArStream;
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
-  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
+  set_staging(a, p, /*resident=*/false, kArStream, kArStream);
   p.nw = kArWaves;
   return true;
 }
 
-static void (*nsf_ar_rt_kernel_of())(NsfArRtArgs) {
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*nsf_ar_rt_kernel_of(const RtPlan&))(NsfArRtArgs) {
   static DeviceMemo attr;
   allow_big_lds(attr, nsf_ar_rt_kernel<kArWaves, kArTiles>);
   return nsf_ar_rt_kernel<kArWaves, kArTiles>;
@@ -175,18 +169,15 @@ static void (*nsf_ar_rt_kernel_of())(NsfArRtArgs) {
 using namespace mnf;
 
 extern "C" int mnf_nsf_ar_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
-  NsfArRtArgs a;
-  RtPlan p;
-  return nsf_ar_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<NsfArRtArgs>([&](NsfArRtArgs& a, RtPlan& p) { return nsf_ar_rt_plan(dim, K, n_hidden, hidden, a, p); });
 }
 
 // workgroups of the launch (each walks the row blocks of 16 x tiles x waves rows blockIdx.x, + grid, ...); 0: no launch, or
 // no device
 extern "C" int64_t mnf_nsf_ar_rt_grid(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
-  NsfArRtArgs a;
-  RtPlan p;
-  if (rows < 1 || !nsf_ar_rt_plan(dim, K, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return persistent_grid(nsf_ar_rt_kernel_of(), p.nw, p.lds, (int64_t)p.nw * kArTiles * 16, rows);
+  return rt_grid_query<NsfArRtArgs>(
+      rows, kArTiles, [&](NsfArRtArgs& a, RtPlan& p) { return nsf_ar_rt_plan(dim, K, n_hidden, hidden, a, p); },
+      nsf_ar_rt_kernel_of);
 }
 
 extern "C" int mnf_nsf_ar_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows, int dim,
@@ -203,6 +194,5 @@ extern "C" int mnf_nsf_ar_rt(const float* x, float* y, float* log_det, int accum
   a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.rows = rows; a.T = tail_bound;
   a.accumulate = accumulate != 0;
   a.vec = dim % 4 == 0 && aligned16(x);
-  return launch_persistent(nsf_ar_rt_kernel_of(), a, p.nw, p.lds, (int64_t)p.nw * kArTiles * 16, rows, "nsf_ar_rt",
-                           (hipStream_t)stream);
+  return launch_plan(nsf_ar_rt_kernel_of(p), a, p, kArTiles, rows, "nsf_ar_rt", (hipStream_t)stream);
 }

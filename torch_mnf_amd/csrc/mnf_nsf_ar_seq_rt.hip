@@ -27,10 +27,8 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_nsf_ar_rt.h"
 #include "mnf_nsf_spline.h"
-#include "mnf_rt.h"
 
 #ifndef MNF_NSF_AR_SEQ_TILES
 #define MNF_NSF_AR_SEQ_TILES 2  // row tiles per wave (1 / 2 / 4: the spline phase uses 16 lanes per tile; profiles/r19/README.md)
@@ -300,22 +298,18 @@ static bool nsf_ar_seq_rt_plan(int dim, int K, int n_hidden, const int* hidden, 
   ArLayout& L = a.L;
   if (dim > kArSeqMaxDim || !ar_seq_has_k(K) || !ar_layout_plan(dim, K, n_hidden, hidden, L)) return false;
   p.mt_max = 1;
-  p.resident = false;
-  a.cb = (dim - 1 + 31) / 32 + n_hidden - 1 + ar_seq_out_tiles(K);
-  a.bt = n_hidden + ar_seq_out_tiles(K);
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
+  set_staging(a, p, /*resident=*/false, (dim - 1 + 31) / 32 + n_hidden - 1 + ar_seq_out_tiles(K), n_hidden + ar_seq_out_tiles(K));
   a.slab_words = 64 * kArSeqTiles * ((dim + 3) / 4);
-  const size_t fixed = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4, slab = (size_t)a.slab_words * 4;
-  int nw = kArSeqMaxWaves;
-  while (nw >= 1 && fixed + nw * slab > 160 * 1024) nw >>= 1;
+  const size_t slab = (size_t)a.slab_words * 4;
+  const int nw = fit_slab_waves(kArSeqMaxWaves, p.lds, slab);
   if (nw < 1) return false;
   p.nw = nw;
-  p.lds = fixed + nw * slab;
+  p.lds += nw * slab;
   return true;
 }
 
-static void (*nsf_ar_seq_rt_kernel_of())(NsfArSeqRtArgs) {
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*nsf_ar_seq_rt_kernel_of(const RtPlan&))(NsfArSeqRtArgs) {
   static DeviceMemo attr;
   allow_big_lds(attr, nsf_ar_seq_rt_kernel<kArSeqTiles>);
   return nsf_ar_seq_rt_kernel<kArSeqTiles>;
@@ -326,18 +320,16 @@ static void (*nsf_ar_seq_rt_kernel_of())(NsfArSeqRtArgs) {
 using namespace mnf;
 
 extern "C" int mnf_nsf_ar_seq_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
-  NsfArSeqRtArgs a;
-  RtPlan p;
-  return nsf_ar_seq_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<NsfArSeqRtArgs>(
+      [&](NsfArSeqRtArgs& a, RtPlan& p) { return nsf_ar_seq_rt_plan(dim, K, n_hidden, hidden, a, p); });
 }
 
 // workgroups of the launch (each walks the row blocks of 16 x tiles x waves rows blockIdx.x, + grid, ...); 0: no launch, or
 // no device
 extern "C" int64_t mnf_nsf_ar_seq_rt_grid(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
-  NsfArSeqRtArgs a;
-  RtPlan p;
-  if (rows < 1 || !nsf_ar_seq_rt_plan(dim, K, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  return persistent_grid(nsf_ar_seq_rt_kernel_of(), p.nw, p.lds, (int64_t)p.nw * kArSeqTiles * 16, rows);
+  return rt_grid_query<NsfArSeqRtArgs>(
+      rows, kArSeqTiles, [&](NsfArSeqRtArgs& a, RtPlan& p) { return nsf_ar_seq_rt_plan(dim, K, n_hidden, hidden, a, p); },
+      nsf_ar_seq_rt_kernel_of);
 }
 
 extern "C" int mnf_nsf_ar_seq_rt(const float* x, float* y, float* log_det, int accumulate, const float* flat, int64_t rows,
@@ -354,6 +346,5 @@ extern "C" int mnf_nsf_ar_seq_rt(const float* x, float* y, float* log_det, int a
   a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.rows = rows; a.T = tail_bound;
   a.accumulate = accumulate != 0;
   a.vec = dim % 4 == 0 && aligned16(y);
-  return launch_persistent(nsf_ar_seq_rt_kernel_of(), a, p.nw, p.lds, (int64_t)p.nw * kArSeqTiles * 16, rows, "nsf_ar_seq_rt",
-                           (hipStream_t)stream);
+  return launch_plan(nsf_ar_seq_rt_kernel_of(p), a, p, kArSeqTiles, rows, "nsf_ar_seq_rt", (hipStream_t)stream);
 }

@@ -17,7 +17,6 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_nsf_spline_grad.h"
 #include "mnf_rt_bwd.h"
 
@@ -39,7 +38,7 @@ struct NsfBwdRtArgs {
   int cb, bt, block_words, bias_words;
   int ht_tiles, dt_tiles, ct_tiles;
   NetDesc f1, f2;
-  int64_t slot_floats;  // 0; mnf_nsf_cl_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_host.h)
+  int64_t slot_floats;  // 0; mnf_nsf_cl_bwd_rt_det: workgroup b adds into grad_flat + b * slot_floats (mnf_rt_host.h)
 };
 
 // the tv-th parameter tile of a slot (widths | heights | derivatives, four positions per tile) -> first position 16 c + k0
@@ -275,27 +274,27 @@ static bool nsf_bwd_rt_plan(int dim, int K, int n_hidden, const int* hidden, Nsf
   sizes[0] = H;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   sizes[n_hidden + 1] = P * H;
-  if (w.min < 4 || w.max > 64 || (int64_t)P * H * w.max >= (1ll << 30)) return false;
-  int64_t off = fill_net(a.f1, n_hidden + 2, sizes, 0);
-  off += fill_net(a.f2, n_hidden + 2, sizes, off);
-  a.n_params = (int)off;
+  if (w.min < 4 || w.max > 64) return false;
+  const int64_t n_params = nsf_cl_layout(n_hidden, sizes, w.max, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   p.mt_max = 4;
   const int TV = nsfb_tiles(K), MTh = (hidden[n_hidden - 1] + 15) / 16, KS = (16 * MTh + 31) / 32, KSO = (TV + 1) / 2;
   a.cb = TV * KS + KSO * MTh;  // a slot: its output tiles' blocks and their turned counterparts
   if (a.cb < 8) a.cb = 8;
   if (a.cb > 40) return false;
   a.bt = TV > p.mt_max ? TV : p.mt_max;
-  a.block_words = 2 * a.cb * rt::kBlockWords;
-  a.bias_words = 2 * a.bt * 16;
   a.ht_tiles = w.tiles;
   a.dt_tiles = 0;  // (the deltas reuse the hidden vectors' tiles: mnf_rt_bwd.h backward_tail)
-  a.ct_tiles = TV > p.mt_max ? TV : p.mt_max;
-  for (p.nw = 8; p.nw >= 1; --p.nw) {  // (any wave count: 6 or 7 waves where 8 do not fit)
-    p.lds = (size_t)4 * rt::kBwdHeadWords + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4 +
-            rt::bwd_lds_bytes(p.nw, a.ht_tiles, a.dt_tiles, a.ct_tiles);
-    if (p.lds <= 160 * 1024) return true;
-  }
-  return false;
+  // (one chunk size, a.bt tiles; any wave count: 6 or 7 waves where 8 do not fit)
+  return rt::fit_bwd_lds(a, a, p, {/*nw_max=*/8, a.cb, a.cb, 1, /*ks1=*/1, /*ct_min=*/a.bt, /*ct_max=*/a.bt});
+}
+
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*nsf_bwd_rt_kernel_of(const RtPlan&))(NsfBwdRtArgs) {
+  static DeviceMemo attr;
+  allow_big_lds(attr, nsf_bwd_rt_kernel<4>);
+  return nsf_bwd_rt_kernel<4>;
 }
 
 }  // namespace mnf
@@ -303,22 +302,16 @@ static bool nsf_bwd_rt_plan(int dim, int K, int n_hidden, const int* hidden, Nsf
 using namespace mnf;
 
 extern "C" int mnf_nsf_cl_bwd_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
-  NsfBwdRtArgs a;
-  RtPlan p;
-  return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? 1 : 0;
+  return rt_has_plan<NsfBwdRtArgs>([&](NsfBwdRtArgs& a, RtPlan& p) { return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p); });
 }
-
-static DeviceMemo nsf_bwd_rt_attr;
 
 extern "C" int64_t mnf_nsf_cl_bwd_rt_det_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
-  NsfBwdRtArgs a;
-  RtPlan p;
-  if (rows < 1 || rows * dim >= (1ll << 40) || !nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) || !gfx950_visible()) return 0;
-  allow_big_lds(nsf_bwd_rt_attr, nsf_bwd_rt_kernel<4>);
-  return rt_det_workspace(nsf_bwd_rt_kernel<4>, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params);
+  return rt_det_workspace<NsfBwdRtArgs>(
+      rows, dim, [&](NsfBwdRtArgs& a, RtPlan& p) { return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? a.n_params : 0; },
+      nsf_bwd_rt_kernel_of);
 }
 
-// det: fixed-order parameter sums through `workspace` (mnf_host.h launch_rt_bwd)
+// det: fixed-order parameter sums through `workspace` (mnf_rt_host.h run_rt_bwd)
 static int nsf_bwd_rt_run(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,
                           float* grad_flat, const float* flat, const float* grad_scale_dev, int64_t rows, int dim, int K,
                           float tail_bound, int inverse, int n_hidden, const int* hidden, bool det, float* workspace,
@@ -326,20 +319,16 @@ static int nsf_bwd_rt_run(const float* x, const float* y, const float* grad_y, c
   if (!x || !y || !grad_x || !flat || !grad_scale_dev || rows < 0 || dim < 2 || (dim & 1) || K < 1 || !(tail_bound > 0.f) ||
       !hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
-  if (det && grad_flat && rows > 0 && (!workspace || workspace_floats < 1)) return MNF_ERR_INVALID_ARG;
-  if (1e-3 * K > 1.0) return MNF_ERR_DOMAIN;
-  if (rows == 0) return MNF_OK;
-  if ((!det && deterministic()) || rows * dim >= (1ll << 40)) return MNF_ERR_UNSUPPORTED;
-  NsfBwdRtArgs a;
-  memset(&a, 0, sizeof(a));
-  RtPlan p;
-  if (!nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p)) return MNF_ERR_UNSUPPORTED;
-  a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
-  a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound; a.inverse = inverse != 0;
-  a.vec = dim % 8 == 0 && aligned16(x, y, grad_x, grad_y);
-  allow_big_lds(nsf_bwd_rt_attr, nsf_bwd_rt_kernel<4>);
-  return launch_rt_bwd(nsf_bwd_rt_kernel<4>, a, p.nw, p.lds, (int64_t)16 * p.nw, rows, a.n_params, det, workspace,
-                       workspace_floats, "nsf_bwd_rt", (hipStream_t)stream);
+  auto fill = [&](NsfBwdRtArgs& a) {
+    a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat; a.flat = flat;
+    a.gscale_dev = grad_scale_dev; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound; a.inverse = inverse != 0;
+    a.vec = dim % 8 == 0 && aligned16(x, y, grad_x, grad_y);
+  };
+  return run_rt_bwd<NsfBwdRtArgs>(
+      {rows, dim, grad_flat, det, workspace, workspace_floats, "nsf_bwd_rt", stream}, /*in_domain=*/1e-3 * K <= 1.0,
+      /*unsupported=*/false,
+      [&](NsfBwdRtArgs& a, RtPlan& p) { return nsf_bwd_rt_plan(dim, K, n_hidden, hidden, a, p) ? a.n_params : 0; }, fill,
+      nsf_bwd_rt_kernel_of);
 }
 
 extern "C" int mnf_nsf_cl_bwd_rt(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x,

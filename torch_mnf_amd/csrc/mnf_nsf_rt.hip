@@ -15,9 +15,8 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_nsf_spline.h"
-#include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 
@@ -204,34 +203,29 @@ static bool nsf_rt_plan(int dim, int K, int n_hidden, const int* hidden, bool al
   sizes[0] = H;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   sizes[n_hidden + 1] = P * H;  // spline_flow.py:246
-  if (w.min < 4 || w.max > 64 || (int64_t)P * H * w.max >= (1ll << 30)) return false;
-  int64_t off = fill_net(a.f1, n_hidden + 2, sizes, 0);
-  off += fill_net(a.f2, n_hidden + 2, sizes, off);
-  a.n_params = (int)off;
+  if (w.min < 4 || w.max > 64) return false;
+  const int64_t n_params = nsf_cl_layout(n_hidden, sizes, w.max, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   a.vec = dim % 8 == 0 && aligned;
-  // the resident image: both nets, blocks and bias tiles
-  int64_t n_blocks = 0, n_bias = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    const int in_cols = l == 0 ? H : 16 * ((sizes[l] + 15) / 16);
-    n_blocks += (int64_t)((in_cols + 31) / 32) * ((sizes[l + 1] + 15) / 16);
-    n_bias += (sizes[l + 1] + 15) / 16;
-  }
+  // the resident image: both nets -- the hidden layers, then the valid tiles of the output layer
+  StagedTiles image = mlp_tiles(sizes, n_hidden, H);
   const int KS = (16 * ((sizes[n_hidden] + 15) / 16) + 31) / 32, TV = nsf_tiles_valid(K), S = 4 * ((H + 15) / 16);
-  n_blocks += (int64_t)S * TV * KS;
-  n_bias += (int64_t)S * TV;
-  n_blocks *= 2;
-  n_bias *= 2;
+  image.blocks = 2 * (image.blocks + (int64_t)S * TV * KS);
+  image.bias = 2 * (image.bias + (int64_t)S * TV);
   constexpr int kStream = 24;  // blocks and bias tiles per streaming buffer
-  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
+  plan_staging(a, p, image, /*resident_bytes=*/150 * 1024, kStream);
   if (!p.resident && TV * KS > kStream) return false;
   p.mt_max = 4;
-  a.cb = p.resident ? (int)n_blocks : kStream;
-  a.bt = p.resident ? (int)n_bias : kStream;
-  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
-  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
-  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
-  p.nw = p.resident && p.lds <= 79 * 1024 ? 4 : 8;
+  p.nw = rt_fwd_waves(p);
   return true;
+}
+
+// the plan's kernel, its dynamic-LDS attribute set
+static void (*nsf_rt_kernel_of(const RtPlan& p))(NsfRtArgs) {
+  static DeviceMemo attr;
+  allow_big_lds(attr, nsf_rt_kernel<4, 8, true>, nsf_rt_kernel<4, 8, false>);
+  return p.resident ? nsf_rt_kernel<4, 8, true> : nsf_rt_kernel<4, 8, false>;
 }
 
 // MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
@@ -244,16 +238,12 @@ int nsf_rt_launch(const float* x, float* y, float* log_det, int accumulate, cons
   if (!nsf_rt_plan(dim, K, n_hidden, hidden, aligned16(x, y), a, p)) return MNF_ERR_UNSUPPORTED;
   a.x = x; a.y = y; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim; a.K = K; a.T = tail_bound;
   a.inverse = inverse != 0; a.accumulate = accumulate != 0;
-  static DeviceMemo attr;
-  allow_big_lds(attr, nsf_rt_kernel<4, 8, true>, nsf_rt_kernel<4, 8, false>);
-  auto kernel = p.resident ? nsf_rt_kernel<4, 8, true> : nsf_rt_kernel<4, 8, false>;
-  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, rows, "nsf_rt", stream);
+  return launch_plan(nsf_rt_kernel_of(p), a, p, 1, rows, "nsf_rt", stream);
 }
 
 }  // namespace mnf
 
 extern "C" int mnf_nsf_cl_rt_supported(int dim, int K, int n_hidden, const int* hidden) {
-  mnf::NsfRtArgs a;
-  mnf::RtPlan p;
-  return mnf::nsf_rt_plan(dim, K, n_hidden, hidden, true, a, p) ? 1 : 0;
+  return mnf::rt_has_plan<mnf::NsfRtArgs>(
+      [&](mnf::NsfRtArgs& a, mnf::RtPlan& p) { return mnf::nsf_rt_plan(dim, K, n_hidden, hidden, true, a, p); });
 }

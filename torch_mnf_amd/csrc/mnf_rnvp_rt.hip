@@ -11,9 +11,8 @@
 
 #include <cstring>
 
-#include "mnf_host.h"
 #include "mnf_rnvp_common.h"
-#include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 
@@ -158,49 +157,37 @@ static bool rnvp_rt_plan(int dim, int n_hidden, const int* hidden, bool aligned,
   sizes[0] = dim;
   const HiddenWidths w = scan_hidden(n_hidden, hidden, sizes);
   if (w.min < 4 || w.max > 256) return false;
-  int64_t off = fill_net(a.net, n_hidden + 1, sizes, 0);
-  const int hl = hidden[n_hidden - 1];
-  a.t_w = (int)off; off += (int64_t)hl * dim;
-  a.t_b = (int)off; off += dim;
-  a.s_w = (int)off; off += (int64_t)hl * dim;
-  a.s_b = (int)off; off += dim;
-  if (off >= (1ll << 31)) return false;
-  a.n_params = (int)off;
+  const int64_t n_params = rnvp_layout(dim, n_hidden, sizes, a);
+  if (!n_params) return false;
+  a.n_params = (int)n_params;
   a.vec = dim % 4 == 0 && aligned;
-  int64_t n_blocks = 0, n_bias = 0;
-  for (int l = 0; l < n_hidden; ++l) {
-    const int in_cols = l == 0 ? dim : 16 * ((sizes[l] + 15) / 16);
-    n_blocks += (int64_t)((in_cols + 31) / 32) * ((sizes[l + 1] + 15) / 16);
-    n_bias += (sizes[l + 1] + 15) / 16;
-  }
-  const int KS = (16 * ((hl + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
-  n_blocks += 2ll * KS * M;
-  n_bias += 2ll * M;
+  // the resident image: the net, then the two heads
+  StagedTiles image = mlp_tiles(sizes, n_hidden, dim);
+  const int KS = (16 * ((hidden[n_hidden - 1] + 15) / 16) + 31) / 32, M = (dim + 15) / 16;
+  image.blocks += 2ll * KS * M;
+  image.bias += 2ll * M;
   // Rows that are not 16-byte aligned (dim not a multiple of 4, a view at an odd offset) have the resident variant only,
   // except in the widest class, whose streaming kernel takes the alignment at run time (a branch around every row access:
   // 15-20 % on the memory-bound shapes) and serves every width: such a call goes there.
-  constexpr int kStream = 16;  // blocks and bias tiles per streaming buffer
-  p.resident = n_blocks * 2048 + n_bias * 64 <= 150 * 1024;
-  p.mt_max = !p.resident && !a.vec ? 16 : w.max <= 64 ? 4 : w.max <= 128 ? 8 : 16;
-  a.cb = p.resident ? (int)n_blocks : kStream;
-  a.bt = p.resident ? (int)n_bias : kStream;
-  a.block_words = (p.resident ? 1 : 2) * a.cb * rt::kBlockWords;
-  a.bias_words = (p.resident ? 1 : 2) * a.bt * 16;
-  p.lds = 64 + (size_t)a.block_words * 4 + (size_t)a.bias_words * 4;
-  // (streaming: every wave of the CU shares one conversion of the weights)
-  p.nw = p.mt_max == 16 || (p.resident && p.lds <= 79 * 1024) ? 4 : 8;
+  plan_staging(a, p, image, /*resident_bytes=*/150 * 1024, /*stream=*/16);
+  p.mt_max = !p.resident && !a.vec ? 16 : rt_size_class(w.max);
+  p.nw = rt_fwd_waves(p);
   return true;
 }
 
+// the plan's kernel (vec: the arguments' a.vec), its dynamic-LDS attribute set
 template <int MT_MAX, int NW>
-static int rnvp_rt_launch_class(const RnvpRtArgs& a, const RtPlan& p, hipStream_t stream) {
+static void (*rnvp_rt_kernel_class(const RtPlan& p, bool vec))(RnvpRtArgs) {
   constexpr int kStreamVec = MT_MAX == 16 ? 2 : 1;
   static DeviceMemo attr;
   allow_big_lds(attr, rnvp_rt_kernel<MT_MAX, NW, true, 1>, rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>,
                 rnvp_rt_kernel<MT_MAX, NW, true, 0>);
-  auto kernel = !p.resident ? rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>
-                            : a.vec ? rnvp_rt_kernel<MT_MAX, NW, true, 1> : rnvp_rt_kernel<MT_MAX, NW, true, 0>;
-  return launch_persistent(kernel, a, p.nw, p.lds, (int64_t)p.nw * 16, a.rows, "rnvp_rt", stream);
+  return !p.resident ? rnvp_rt_kernel<MT_MAX, NW, false, kStreamVec>
+                     : vec ? rnvp_rt_kernel<MT_MAX, NW, true, 1> : rnvp_rt_kernel<MT_MAX, NW, true, 0>;
+}
+static void (*rnvp_rt_kernel_of(const RtPlan& p, bool vec))(RnvpRtArgs) {
+  return p.mt_max == 4 ? rnvp_rt_kernel_class<4, 8>(p, vec)
+                       : p.mt_max == 8 ? rnvp_rt_kernel_class<8, 8>(p, vec) : rnvp_rt_kernel_class<16, 4>(p, vec);
 }
 
 // MNF_ERR_UNSUPPORTED: the shape is outside the run-time-shaped kernel too (the caller runs the VALU kernel)
@@ -213,15 +200,12 @@ int rnvp_rt_launch(const float* z, const float* mask, uint64_t seed, float* x, f
   if (!rnvp_rt_plan(dim, n_hidden, hidden, aligned16(z, x, mask), a, p)) return MNF_ERR_UNSUPPORTED;
   a.z = z; a.mask = mask; a.seed = seed; a.x = x; a.log_det = log_det; a.flat = flat; a.rows = rows; a.dim = dim;
   a.accumulate = accumulate != 0;
-  if (p.mt_max == 4) return rnvp_rt_launch_class<4, 8>(a, p, stream);
-  if (p.mt_max == 8) return rnvp_rt_launch_class<8, 8>(a, p, stream);
-  return rnvp_rt_launch_class<16, 4>(a, p, stream);
+  return launch_plan(rnvp_rt_kernel_of(p, a.vec != 0), a, p, 1, rows, "rnvp_rt", stream);
 }
 
 }  // namespace mnf
 
 extern "C" int mnf_rnvp_rt_supported(int dim, int n_hidden, const int* hidden) {
-  mnf::RnvpRtArgs a;
-  mnf::RtPlan p;
-  return mnf::rnvp_rt_plan(dim, n_hidden, hidden, true, a, p) ? 1 : 0;
+  return mnf::rt_has_plan<mnf::RnvpRtArgs>(
+      [&](mnf::RnvpRtArgs& a, mnf::RtPlan& p) { return mnf::rnvp_rt_plan(dim, n_hidden, hidden, true, a, p); });
 }

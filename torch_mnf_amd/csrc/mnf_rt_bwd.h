@@ -12,9 +12,10 @@
 // finished 16 x 16 block of dW is added to grad_flat with float atomics: ONE flush per row block instead of per tile,
 // no accumulator registers, any layer width.  (Atomic sums: not bit-reproducible run to run.  The (m, n) pairs go to the
 // waves by shape alone, so one lane makes every add to a given dW / db entry of a workgroup: with a slot of its own per
-// workgroup (mnf_host.h launch_rt_bwd, the *_bwd_rt_det entries) the sums repeat bit for bit.)
+// workgroup (mnf_rt_host.h launch_rt_bwd, the *_bwd_rt_det entries) the sums repeat bit for bit.)
 #pragma once
 #include "mnf_rt.h"
+#include "mnf_rt_host.h"
 
 namespace mnf {
 namespace rt {
@@ -455,6 +456,40 @@ __device__ __forceinline__ BwdLds bwd_lds(uint32_t* lds0, float* after_weights, 
 inline size_t bwd_lds_bytes(int nw, int ht_tiles, int dt_tiles, int ct_tiles) {
   const size_t tile_bytes = (size_t)2 * 16 * (16 * nw + kExPad) * 2;
   return (size_t)(ht_tiles + dt_tiles + ct_tiles) * tile_bytes + (size_t)nw * (kMaxBwdLayers + 1) * 64 * 4;
+}
+// Blocks per streaming buffer of a net with two heads behind its last hidden layer of hl units (host): a round of the heads
+// -- 2 tiles x 2 heads x KSh blocks, then 2 x MTh turned ones --, a K-step of the first layer (h0 units), at least 8
+inline int bwd_head_round_blocks(int hl, int h0) {
+  const int MTh = (hl + 15) / 16, KSh = (16 * MTh + 31) / 32, MT1 = (h0 + 15) / 16;
+  const int cb = 4 * KSh > 2 * MTh ? 4 * KSh : 2 * MTh;
+  return cb < MT1 ? (MT1 < 8 ? 8 : MT1) : cb < 8 ? 8 : cb;
+}
+// The LDS fit of a gradient launch (host): the head, two streaming buffers of cb blocks and s.bt bias tiles, and behind them
+// the exchange area of a.ht_tiles hidden tiles (the deltas reuse them: backward_tail) and ct chunk tiles.  Rows per
+// workgroup first -- nw_max waves down to one, any count -- then the weight stream from cb_hi down to cb_lo blocks per buffer
+// in steps of cb_step, then as many first-layer input tiles per chunk as a buffer holds K-steps of them (cb / ks1, within
+// ct_min .. ct_max), then ct_min.  Fills p.nw, p.lds, the stream's part of `s` and a.ct_tiles, or says no.
+struct BwdFit {
+  int nw_max, cb_hi, cb_lo, cb_step, ks1, ct_min, ct_max;
+};
+template <typename Stream, typename Args>
+inline bool fit_bwd_lds(Stream& s, Args& a, RtPlan& p, const BwdFit& f) {
+  s.bias_words = 2 * s.bt * 16;
+  for (p.nw = f.nw_max; p.nw >= 1; --p.nw) {
+    for (int cb = f.cb_hi; cb >= f.cb_lo; cb -= f.cb_step) {
+      int ci = cb / f.ks1;
+      ci = ci > f.ct_max ? f.ct_max : ci < f.ct_min ? f.ct_min : ci;
+      for (int ct = ci; ct >= f.ct_min; ct = ct > f.ct_min ? f.ct_min : 0) {
+        s.cb = cb;
+        s.block_words = 2 * cb * kBlockWords;
+        a.ct_tiles = ct;
+        p.lds = (size_t)4 * kBwdHeadWords + (size_t)s.block_words * 4 + (size_t)s.bias_words * 4 +
+                bwd_lds_bytes(p.nw, a.ht_tiles, 0, ct);
+        if (p.lds <= kRtLdsBytes) return true;
+      }
+    }
+  }
+  return false;
 }
 
 // The forward recompute of one conditioner net that KEEPS every hidden vector: its true values turned into the exchange
