@@ -1,7 +1,9 @@
 """Run by tests/test_hip_maf_rt.py in a child process under MNF_DETERMINISTIC=1 (the switch is read once per process): the
 one-pass direction of MAF lands on maf_bwd_rt in its fixed-order form -- two backward passes of one shape give bit-identical
 parameter gradients, no atomic-sums warning, the gradients within the float64 oracle's budget --, the atomic entry refuses,
-and the element-by-element direction (VALU kernel, atomic sums) still warns.  Prints "maf rt deterministic child ok"."""
+the element-by-element direction (VALU kernel, atomic sums) still warns, and the cot_small, cot_outlier and big_rows gradient
+cases of one layer of tests/maf_rt_range_cases.py hold in this mode with the same budget, two passes bit-identical.  Prints
+"maf rt deterministic child ok"."""
 import os
 import sys
 import warnings
@@ -14,6 +16,7 @@ for p in (ROOT, HERE, os.path.join(HERE, "golden")):
 
 import torch  # noqa: E402
 
+import maf_rt_range_cases as M  # noqa: E402
 import recipes  # noqa: E402
 import torch_mnf_amd as amd  # noqa: E402
 from oracle import flow_oracle as O  # noqa: E402
@@ -75,6 +78,10 @@ def main():
         torch.cuda.synchronize()
     assert amd.last_kernel() == "maf_bwd_generic", amd.last_kernel()
     assert any("MNF_DETERMINISTIC" in str(m.message) for m in caught)
+    # the range table's gradient cases of one layer on the fixed-order kernel
+    n = M.run_deterministic(amd, M.DETERMINISTIC_LAYER, inverse=True)
+    assert n == 3, n
+    print(f"range: {n} gradient cases of {M.DETERMINISTIC_LAYER} on maf_bwd_rt within the oracle budget, twice, bit for bit")
     print("maf rt deterministic child ok")
 
 

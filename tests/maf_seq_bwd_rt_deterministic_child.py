@@ -1,8 +1,9 @@
 """Run by tests/test_hip_maf_seq_bwd_rt.py in a child process under MNF_DETERMINISTIC=1 (the switch is read once per
 process): with the route opted in, the gradients of the element-by-element direction of MAF land on maf_seq_bwd_rt in its
 fixed-order form (mnf_maf_seq_bwd_rt_det: the solve has no sums, the weight pass is mnf_maf_bwd_rt_det) -- two backward
-passes of one shape give bit-identical gradients, within the float64 oracle's budget, and no atomic-sums warning.  Prints
-"maf seq bwd rt deterministic child ok"."""
+passes of one shape give bit-identical gradients, within the float64 oracle's budget, and no atomic-sums warning; the
+cot_small, cot_outlier and big_rows gradient cases of one layer of tests/maf_rt_range_cases.py hold in this mode with the same
+budget, two passes bit-identical.  Prints "maf seq bwd rt deterministic child ok"."""
 import os
 import sys
 import warnings
@@ -15,6 +16,7 @@ for p in (ROOT, HERE, os.path.join(HERE, "golden")):
 
 import torch  # noqa: E402
 
+import maf_rt_range_cases as M  # noqa: E402
 import recipes  # noqa: E402
 import torch_mnf_amd as amd  # noqa: E402
 from oracle import flow_oracle as O  # noqa: E402
@@ -57,6 +59,10 @@ def main():
         ref.check_all(runs[0], f"deterministic maf_seq_bwd_rt d={dim} h={h_sizes} rows={rows}")
         for m in layer._masked():
             assert float((m.weight.grad * (m.mask.T == 0)).abs().max()) == 0.0
+    # the range table's gradient cases of one layer on the fixed-order route
+    n = M.run_deterministic(amd, M.DETERMINISTIC_LAYER, inverse=False)
+    assert n == 3, n
+    print(f"range: {n} gradient cases of {M.DETERMINISTIC_LAYER} on maf_seq_bwd_rt within the oracle budget, twice, bit for bit")
     print("maf seq bwd rt deterministic child ok")
 
 

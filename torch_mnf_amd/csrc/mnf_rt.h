@@ -414,7 +414,7 @@ __device__ __forceinline__ void split_kstep(const f32x4& a, const f32x4& b, floa
 }
 
 // Accumulators -> activations -> the next layer's split tiles.  pre = (main + corr 2^-11) * scale + bias; the activation
-// when `act`: LeakyReLU, or -- RELU -- ReLU, slope 0 (MADE, made.py: p < 0 ? 0 : p, i.e. max(p, 0) with a NaN kept as
+// when `act`: LeakyReLU, or -- RELU -- ReLU, slope 0 (MADE, made.py: negative numbers become 0, a NaN is kept as
 // torch.relu keeps it).  scale[t] = wup * (the input rows' factor); tiles >= MT come out as zeros.
 template <int MT_MAX, int NTL, bool RELU = false>
 __device__ __forceinline__ void finish_layer(const Acc<MT_MAX, NTL>& acc, const float* bias_tiles, int MT, int q,
@@ -423,9 +423,17 @@ __device__ __forceinline__ void finish_layer(const Acc<MT_MAX, NTL>& acc, const 
   auto value = [&](int t, int m, const f32x4& bias) {
     const f32x4 p = (acc.corr[t][m] * kSplitInvScale + acc.main[t][m]) * scale[t] + bias;
     if constexpr (RELU) {
+      // The select is on the BITS: these units are built with -fno-honor-nans, under which `p < 0 ? 0 : p` becomes
+      // v_max_f32(p, 0) -- and the hardware's max answers 0 for a NaN, so a row with a non-finite input came out of the
+      // first ReLU as finite numbers (tests/maf_rt_range_cases.py, nonfinite_row).  [0x80000001, 0xff800000] is every
+      // negative number and -inf; a NaN of either sign and -0 stay what they are, as torch.relu leaves them.
       f32x4 v;
 #pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = act && p[r] < 0.f ? 0.f : p[r];
+      for (int r = 0; r < 4; ++r) {
+        const float pr = p[r];  // (a copy: the bit cast of a vector ELEMENT reads the vector's first one)
+        const uint32_t b = __builtin_bit_cast(uint32_t, pr);
+        v[r] = act && b - 0x80000001u <= 0x7f7fffffu ? 0.f : pr;
+      }
       return v;
     } else {
       return act ? __builtin_elementwise_max(p, p * kLeakySlope) : p;

@@ -64,9 +64,23 @@ __device__ __forceinline__ void transpose_store(const u32x2& hi, const u32x2& lo
   *reinterpret_cast<u32x2*>(p + 16 * unit_stride) = ol;
 }
 
+// the signed e that brings v 2^-e into [2^12, 2^13) (0 for v = 0 or a non-finite v: finite_abs) -- a row scaled this way is
+// split the same whatever power of two its cotangents were multiplied by on the way in
+__device__ __forceinline__ int both_exponent(float fm) {
+  const int e = (int)((__builtin_bit_cast(uint32_t, fm) >> 23) & 0xffu) - 127 - 12;
+  return fm > 0.f ? (e < -100 ? -100 : e) : 0;
+}
+// The scale of a delta of the masked (MAF) chain: down_exponent(v, 13), and both_exponent for a maximum below 2^-6.  The
+// deltas are in units of the gradient scale (~1 at the heads), but a MaskedLinear whose weights are 2^-12 of its
+// neighbours' hands on deltas of 2^-14 and less: unscaled those are f16 subnormals throughout, carried to 2^-36 ABSOLUTE,
+// 1e-5 of dW_0 / db_0 (found by tests/maf_rt_range_cases.py `big_hidden`).  From 2^-6 up the scale stays 1, so that ordinary
+// launches keep dw_phase_rows' one-accumulator form and their bits.
+__device__ __forceinline__ int delta_exponent(float fm) { return fm < 0x1p-6f ? both_exponent(fm) : down_exponent(fm, 13); }
+
 // fp32 tiles (accumulator layout) -> exchange tiles with ONE power-of-two scale for the wave's 16 rows (the rows of a
 // tile share an MFMA's K axis): returns 2^e, the factor the tile's products are multiplied back by.  MT tiles used.
-template <int MT_MAX>
+// SMALL_UP: a maximum below 2^-6 is scaled UP as well (delta_exponent: the masked chain's deltas).
+template <int MT_MAX, bool SMALL_UP = false>
 __device__ __forceinline__ float exchange_store(const f32x4 (&v)[MT_MAX], int MT, const Exchange& ex, int tile0, int row0,
                                                 int lane, const f16x4& ident) {
   float mx = 0.f;
@@ -75,7 +89,7 @@ __device__ __forceinline__ float exchange_store(const f32x4 (&v)[MT_MAX], int MT
 #pragma unroll
     for (int r = 0; r < 4; ++r) mx = __builtin_fmaxf(mx, finite_abs(v[m][r]));
   mx = wave_max(mx);
-  const int e = down_exponent(mx, 13);
+  const int e = SMALL_UP ? delta_exponent(mx) : down_exponent(mx, 13);
   const float down = pow2f(-e);
 #pragma unroll
   for (int m = 0; m < MT_MAX; ++m)
@@ -378,14 +392,14 @@ __device__ __forceinline__ void unsplit(const Hidden<MT_MAX, 1>& h, f32x4 (&v)[M
 }
 
 // fp32 tiles -> split tiles with the row's power-of-two scale (the B operands of the next chain product)
-template <int MT_MAX>
+template <int MT_MAX, bool SMALL_UP = false>
 __device__ __forceinline__ void split_rows(const f32x4 (&v)[MT_MAX], Hidden<MT_MAX, 1>& h) {
   float fm = 0.f;
 #pragma unroll
   for (int m = 0; m < MT_MAX; ++m)
 #pragma unroll
     for (int r = 0; r < 4; ++r) fm = __builtin_fmaxf(fm, finite_abs(v[m][r]));
-  const int e = down_exponent(max_over_q(fm), 13);
+  const int e = SMALL_UP ? delta_exponent(max_over_q(fm)) : down_exponent(max_over_q(fm), 13);
   const float down = pow2f(-e);
   h.up[0] = pow2f(e);
   float unused = 0.f;
@@ -393,12 +407,6 @@ __device__ __forceinline__ void split_rows(const f32x4 (&v)[MT_MAX], Hidden<MT_M
   for (int m = 0; m < MT_MAX; ++m) split_tile(v[m] * down, h.hi[0][m], h.lo[0][m], unused);
 }
 
-// the signed e that brings v 2^-e into [2^12, 2^13) (0 for v = 0 or a non-finite v: finite_abs) -- a row scaled this way is
-// split the same whatever power of two its cotangents were multiplied by on the way in
-__device__ __forceinline__ int both_exponent(float fm) {
-  const int e = (int)((__builtin_bit_cast(uint32_t, fm) >> 23) & 0xffu) - 127 - 12;
-  return fm > 0.f ? (e < -100 ? -100 : e) : 0;
-}
 // fp32 tiles -> split tiles with the row's power-of-two scale, UP as well as down: the row's largest entry goes to
 // [2^12, 2^13) (split_rows above only scales down; a one-hot cotangent of a mean loss is ~1/rows and would sit in
 // f16's subnormals).  A row of zeros or non-finite values keeps scale 1.
@@ -533,7 +541,7 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
       // for the deltas, so that more rows fit a workgroup (the per-row-block cost is what these kernels are bound by)
       lds_barrier();
       const Exchange exD{L.exH.tile(exH_tile_of(nd, i)), L.exH.R};
-      const float sc = exchange_store<MT_MAX>(dv, MTi, exD, 0, 16 * wave, lane, L.ident);
+      const float sc = exchange_store<MT_MAX, kMasked>(dv, MTi, exD, 0, 16 * wave, lane, L.ident);
       if (lane == 0) L.sA[wave] = sc;
       lds_barrier();
       if constexpr (kMasked)
@@ -545,7 +553,7 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
     }
     // delta_{i-1} = (W_{i-1}^T delta_i) * act'(H_{i-1}): K = the units of H_i, output tiles = those of H_{i-1}
     Hidden<MT_MAX, 1> hd;
-    split_rows<MT_MAX>(dv, hd);
+    split_rows<MT_MAX, kMasked>(dv, hd);
     const int KS = steps32(16 * MTi);
     int KC = src.cb / MTp;
     if (KC < 1) KC = 1;
@@ -579,11 +587,11 @@ __device__ __forceinline__ void backward_tail(Src& src, const float* __restrict_
   const Exchange exD1{L.exH.tile(exH_tile_of(nd, 1)), L.exH.R};  // (delta_1 in H_1's tiles, as above)
   if (gflat) {
     lds_barrier();
-    const float sc = exchange_store<MT_MAX>(dv, MT1, exD1, 0, 16 * wave, lane, L.ident);
+    const float sc = exchange_store<MT_MAX, kMasked>(dv, MT1, exD1, 0, 16 * wave, lane, L.ident);
     if (lane == 0) L.sA[wave] = sc;
   }
   Hidden<MT_MAX, 1> hd;
-  split_rows<MT_MAX>(dv, hd);
+  split_rows<MT_MAX, kMasked>(dv, hd);
   int CI = src.cb / KS1;
   if (CI > L.ct_tiles) CI = L.ct_tiles;
   if (CI > MT_MAX) CI = MT_MAX;
