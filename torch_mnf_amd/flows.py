@@ -222,6 +222,15 @@ def _home_stand_in(module: nn.Module, device) -> Tensor:
     return t
 
 
+def _flat_input(owner, params, home: tuple | None, device) -> Tensor:
+    """What an autograd Function takes as its flat-parameter input: the owner's stand-in when the parameters live in a
+    flat ``home`` (_flat_home_of), else their concatenation with the autograd link (``params``: the list, or a callable
+    that makes it -- asked only without a home)."""
+    if home is not None:
+        return _home_stand_in(owner, device)
+    return torch.cat([p.reshape(-1) for p in (params() if callable(params) else params)])
+
+
 def _ptr(t: Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
@@ -260,6 +269,39 @@ def _index_on(device, idx) -> Tensor:
     return torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
 
 
+def _device_table(cache: dict, slot, device, build):
+    """THE per-device table cache: built once per ``cache[slot]``, rebuilt when asked for another device.  ``build()``
+    answers a host index table (_counted_index), a tuple of host tables and plain numbers (_layout_index: the tables go
+    to the device, the numbers ride along) or None -- the shape has no such kernel, remembered like a table (the library
+    is not asked again)."""
+    device = torch.device(device)
+    hit = cache.get(slot)
+    if hit is None or hit[0] != device:
+        host = build()
+        if isinstance(host, tuple):
+            host = tuple(_index_on(device, h) if isinstance(h, ctypes.Array) else h for h in host)
+        elif host is not None:
+            host = _index_on(device, host)
+        hit = cache[slot] = (device, host)
+    return hit[1]
+
+
+def _pack_split(lib, flat: Tensor, table: tuple, n: int | None = None, stride: int = 0) -> Tensor:
+    """The split (f16 hi + lo) operand image of the parameters in ``flat``, by ``table`` = (device index table,
+    n_split_words, n_plain_words): n_split + n_plain + MNF_SPLIT_TAIL_WORDS int32 words from one gather launch.  With
+    ``n`` and ``stride``: n images back to back in one buffer, image i from flat[i * stride:], still one launch."""
+    idx, n_split, n_plain = table
+    words = n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS
+    image = torch.empty(words if n is None else n * words, dtype=torch.int32, device=idx.device)
+    if n is None:
+        _lib.check("mnf_pack_gather_split", lib.mnf_pack_gather_split(
+            flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, n_plain, _stream()))
+    else:
+        _lib.check("mnf_pack_gather_split_batch", lib.mnf_pack_gather_split_batch(
+            flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, n_plain, n, stride, _stream()))
+    return image
+
+
 def _device_input(t: Tensor, what: str) -> Tensor:
     if not isinstance(t, Tensor) or not t.is_cuda:
         raise RuntimeError(
@@ -284,6 +326,12 @@ def _empty_result(x: Tensor, accum: Tensor | None):
     return torch.empty_like(x), (None if accum is not None else x.new_empty(0))
 
 
+def _outputs(x: Tensor, accum: Tensor | None) -> tuple[Tensor, Tensor]:
+    """(y, the tensor the launch writes or adds log_det to): ``accum`` itself where the caller handed one."""
+    ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    return torch.empty_like(x), ld
+
+
 def _wants_grad(module: nn.Module, x: Tensor) -> bool:
     return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
 
@@ -301,6 +349,22 @@ def _grad_scale(gy: Tensor | None, gl: Tensor | None, rows: int, dim: int, devic
 
 bwd_kernel_events: list | None = None  # set to a list to collect (start, end) events of every split gradient launch
 rnvp_bwd_kernel_events: list | None = None  # likewise for launch B-ts of every RNVP gradient pass
+
+
+def _mark_start(events: list | None):
+    """bench.py: the (start, end) HIP event pair around a gradient kernel proper, its start recorded -- None unless
+    ``events`` (one of the two lists above) is being collected.  _mark_end closes the pair."""
+    if events is None:
+        return None
+    marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    marks[0].record()
+    return marks
+
+
+def _mark_end(events: list | None, marks) -> None:
+    if marks is not None:
+        marks[1].record()
+        events.append(marks)
 
 
 def _bwd_rt_launch(lib, entry: str, args: tuple, shape: tuple, device, sums: bool = True) -> int:
@@ -348,63 +412,50 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
     False when that form does not exist for this call (nothing has been computed: the caller materialises grad_y)."""
     rows, hid = x_in.shape[0], (len(f.h_sizes), f._hid)
     index = f._bwd_index(x_in.device) if grad_flat_ptr is not None and not f.force_generic else None
+    shape = (rows, f.dim, int(bool(f.parity)), int(inverse), *hid)
+
+    def head(a, b, operands):
+        """The per-shape entries' common leading arguments: two cotangent slots, then the operand image or parameters."""
+        return (x_in.data_ptr(), a, b, gx.data_ptr(), grad_flat_ptr, operands, index.data_ptr(), *shape)
+
     rc = _lib.MNF_ERR_UNSUPPORTED
     if lp_scratch is not None:
         if index is None or bwd_image_ptr is None or gl is None:
             return False
         cap = cold.numel() - 1
-        marks = None
-        if bwd_kernel_events is not None:
-            marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            marks[0].record()
+        marks = _mark_start(bwd_kernel_events)
         rc = lib.mnf_affine_half_bwd_split_lp(
-            x_in.data_ptr(), gl.data_ptr(), lp_scratch.data_ptr(), gx.data_ptr(), grad_flat_ptr, bwd_image_ptr,
-            index.data_ptr(), rows, f.dim, int(bool(f.parity)), int(inverse), *hid, scale.data_ptr(), cold.data_ptr(),
-            cap, _ptr(work), 0 if work is None else work.numel(), _stream())
+            *head(gl.data_ptr(), lp_scratch.data_ptr(), bwd_image_ptr), scale.data_ptr(), cold.data_ptr(), cap,
+            _ptr(work), 0 if work is None else work.numel(), _stream())
         if rc == _lib.MNF_ERR_UNSUPPORTED:
             return False
-        if marks is not None:
-            marks[1].record()
-            bwd_kernel_events.append(marks)
+        _mark_end(bwd_kernel_events, marks)
         _lib.check("mnf_affine_half_bwd_split_lp", rc)
         _lib.check("mnf_affine_half_bwd_mfma_tiles", lib.mnf_affine_half_bwd_mfma_tiles(
-            x_in.data_ptr(), lp_scratch.data_ptr(), gl.data_ptr(), gx.data_ptr(), grad_flat_ptr, flat_ptr,
-            index.data_ptr(), rows, f.dim, int(bool(f.parity)), int(inverse), *hid, cold.data_ptr(), cap, _stream()))
+            *head(lp_scratch.data_ptr(), gl.data_ptr(), flat_ptr), cold.data_ptr(), cap, _stream()))
         return True
     if index is not None and bwd_image_ptr is not None:
         cap = cold.numel() - 1
-        marks = None
-        if bwd_kernel_events is not None:  # bench.py: (start, end) HIP events around the gradient kernel proper
-            marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            marks[0].record()
+        marks = _mark_start(bwd_kernel_events)  # bench.py: (start, end) HIP events around the gradient kernel proper
         rc = lib.mnf_affine_half_bwd_split(
-            x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, bwd_image_ptr, index.data_ptr(), rows,
-            f.dim, int(bool(f.parity)), int(inverse), *hid, scale.data_ptr(), cold.data_ptr(), cap, _ptr(work),
+            *head(_ptr(gy), _ptr(gl), bwd_image_ptr), scale.data_ptr(), cold.data_ptr(), cap, _ptr(work),
             0 if work is None else work.numel(), _stream())
-        if marks is not None:
-            marks[1].record()
-            bwd_kernel_events.append(marks)
+        _mark_end(bwd_kernel_events, marks)
         if rc == _lib.MNF_OK:
-            rc = lib.mnf_affine_half_bwd_mfma_tiles(
-                x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, index.data_ptr(), rows,
-                f.dim, int(bool(f.parity)), int(inverse), *hid, cold.data_ptr(), cap, _stream())
+            rc = lib.mnf_affine_half_bwd_mfma_tiles(*head(_ptr(gy), _ptr(gl), flat_ptr), cold.data_ptr(), cap, _stream())
     if rc == _lib.MNF_ERR_UNSUPPORTED and index is not None:
         n_ws = lib.mnf_affine_half_bwd_mfma_workspace(rows, f.dim, *hid) if _lib.deterministic() else 0
         if n_ws > 0:  # MNF_DETERMINISTIC=1: the workgroups' sums as blocks, added in a fixed order
             ws = torch.empty(n_ws, dtype=torch.float32, device=x_in.device)
-            rc = lib.mnf_affine_half_bwd_mfma_det(
-                x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, index.data_ptr(), rows,
-                f.dim, int(bool(f.parity)), int(inverse), *hid, ws.data_ptr(), n_ws, _stream())
+            rc = lib.mnf_affine_half_bwd_mfma_det(*head(_ptr(gy), _ptr(gl), flat_ptr), ws.data_ptr(), n_ws, _stream())
         else:
-            rc = lib.mnf_affine_half_bwd_mfma(
-                x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, index.data_ptr(), rows,
-                f.dim, int(bool(f.parity)), int(inverse), *hid, _stream())
+            rc = lib.mnf_affine_half_bwd_mfma(*head(_ptr(gy), _ptr(gl), flat_ptr), _stream())
     if rc == _lib.MNF_ERR_UNSUPPORTED and flat_ptr is not None and (y_out is not None or not inverse or not f.scale) \
             and _dispatch.wants_rt(rows, f.force_generic, f._fp32_request()):
         # no per-shape gradient kernel: the run-time-shaped matrix-core one (any 1..4 hidden layers of widths 4..64)
         sc = scale if scale is not None else _grad_scale(gy, gl, rows, f.dim, x_in.device)
         args = (x_in.data_ptr(), _ptr(y_out), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, sc.data_ptr(),
-                rows, f.dim, int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift))
+                *shape, int(f.scale), int(f.shift))
         ws_shape, sums = (rows, f.dim, *hid, int(f.scale), int(f.shift)), grad_flat_ptr is not None
         rc = _bwd_rt_launch(lib, "mnf_affine_half_bwd_rt", args, ws_shape, x_in.device, sums)
         if rc == _lib.MNF_ERR_UNSUPPORTED and _ahf_bwd_rt_wide(lib, f, rows):
@@ -412,14 +463,14 @@ def _ahf_layer_backward(lib, f, x_in: Tensor, gy, gl, gx: Tensor, grad_flat_ptr,
             rc = _bwd_rt_launch(lib, "mnf_affine_half_bwd_rt_wide", args, ws_shape, x_in.device, sums)
     if rc == _lib.MNF_ERR_UNSUPPORTED:  # no matrix-core gradient kernel for this shape at all
         rc = lib.mnf_affine_half_bwd(
-            x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, rows, f.dim,
-            int(bool(f.parity)), int(inverse), *hid, int(f.scale), int(f.shift), _stream())
+            x_in.data_ptr(), _ptr(gy), _ptr(gl), gx.data_ptr(), grad_flat_ptr, flat_ptr, *shape, int(f.scale),
+            int(f.shift), _stream())
     _lib.check("mnf_affine_half_bwd", rc)
-    shape = f"dim={f.dim}, hidden={f.h_sizes}"
+    what = f"dim={f.dim}, hidden={f.h_sizes}"
     if not f.force_generic:
-        _lib.note_generic("AffineHalfFlow.backward", rows, shape)
+        _lib.note_generic("AffineHalfFlow.backward", rows, what)
     if grad_flat_ptr is not None:
-        _lib.note_atomic_sums("AffineHalfFlow.backward", shape)
+        _lib.note_atomic_sums("AffineHalfFlow.backward", what)
     return True
 
 
@@ -438,14 +489,8 @@ class _AffineHalfFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, inverse):
-        flat, image = module._packed(x.device)
-        y = torch.empty_like(x)
-        ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_affine_half", _lib.load().mnf_affine_half(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), 0, _ptr(flat), _ptr(image), _ptr(module._split_image(x.device)),
-            x.shape[0], module.dim,
-            int(bool(module.parity)), int(inverse), len(module.h_sizes), module._hid, int(module.scale),
-            int(module.shift), module._force_code(image), _stream()))
+        y, ld = _outputs(x, None)
+        flat = module._forward_launch(x, y, ld, 0, inverse, None)
         ctx.module, ctx.inverse = module, inverse
         # (y too: the run-time-shaped gradient kernel forms the inverse direction's g_s = -grad_y y - grad_ld from it; the
         #  next layer keeps its input alive anyway)
@@ -479,16 +524,8 @@ class _NsfFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, inverse):
-        flat, image = module._packed(x.device)
-        y = torch.empty_like(x)
-        ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        _lib.check("mnf_nsf_cl", _lib.load().mnf_nsf_cl(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), 0, _ptr(flat), _ptr(image), _ptr(module._split_image(x.device)),
-            x.shape[0], module.dim,
-            module.K, float(module.B), int(inverse), len(module.h_sizes), module._hid,
-            module._force_code(image), _stream()))
-        if not module.force_generic and not module._pad_half():  # (a padded-twin shape is here by choice: few rows)
-            _lib.note_generic("NSF_CL", x.shape[0], f"dim={module.dim}, K={module.K}, hidden={module.h_sizes}")
+        y, ld = _outputs(x, None)
+        flat = module._forward_launch(x, y, ld, 0, inverse)
         ctx.module, ctx.inverse = module, inverse
         # (y too: the tile gradient kernel reads the second net's conditioner input out of it instead of recomputing the
         #  first half-step; the next layer keeps its input alive anyway)
@@ -513,29 +550,21 @@ class _NsfFn(torch.autograd.Function):
         if not (m.force_generic or m.force_fp32_mfma or _FP32_MFMA_ENV or _dispatch.NSF_BWD_KERNEL == "generic"
                 or rows * m.dim >= (1 << 31)):
             table = m._bwd_tile_tables(x.device)
-        marks = None
-        if bwd_kernel_events is not None and table:  # bench.py --workload c3t
-            marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         if table:
             idx, flush, n_split, n_plain = table
-            image = torch.empty(n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32, device=x.device)
-            _lib.check("mnf_pack_gather_split", lib.mnf_pack_gather_split(
-                flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, n_plain, _stream()))
+            image = _pack_split(lib, flat, (idx, n_split, n_plain))
             scale = _grad_scale(gy, gl, rows, m.dim, x.device)
             cap = (rows + 15) // 16
             cold = torch.zeros(2 * cap + 2, dtype=torch.int32, device=x.device)
             n_work = lib.mnf_nsf_cl_bwd_tile_workspace(rows, m.dim, m.K, len(m.h_sizes), m._hid)
             work = torch.empty(n_work, dtype=torch.float32, device=x.device)
-            if marks is not None:
-                marks[0].record()
+            marks = _mark_start(bwd_kernel_events)  # bench.py --workload c3t
             rc = lib.mnf_nsf_cl_bwd_tile(
                 x.data_ptr(), y_out.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(),
                 image.data_ptr(), flush.data_ptr(), *args, scale.data_ptr(), cold.data_ptr(), cap, work.data_ptr(), n_work, _stream())
             if rc != _lib.MNF_ERR_UNSUPPORTED:  # (unsupported: e.g. a view at an odd storage offset -- the kernels below take it)
                 _lib.check("mnf_nsf_cl_bwd_tile", rc)
-                if marks is not None:
-                    marks[1].record()
-                    bwd_kernel_events.append(marks)
+                _mark_end(bwd_kernel_events, marks)
                 _lib.check("mnf_nsf_cl_bwd_tile_fixup", lib.mnf_nsf_cl_bwd_tile_fixup(
                     x.data_ptr(), _ptr(gy), _ptr(gl), grad_x.data_ptr(), grad_flat.data_ptr(), flat.data_ptr(), *args,
                     cold.data_ptr(), cap, _stream()))
@@ -568,8 +597,7 @@ class _RnvpFn(torch.autograd.Function):
         few = module._few(z.shape[0], mask is not None)
         flat, image = module._packed(z.device, images=not few)
         ctx.home = home
-        x = torch.empty_like(z)
-        ld = torch.empty(z.shape[0], dtype=torch.float32, device=z.device)
+        x, ld = _outputs(z, None)
         lib = _lib.load()
         # a large batch: the split forward kernels can keep y = net(mask * z) (64 floats per row) for the matrix-core
         # gradient pass, whose first launch then skips its own sweep over z
@@ -634,11 +662,9 @@ class _RnvpFn(torch.autograd.Function):
             else:  # bench.py: HIP events around launch B-ts, the pass's dominant kernel
                 rc = go(1)
                 if rc == _lib.MNF_OK:
-                    marks = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                    marks[0].record()
+                    marks = _mark_start(rnvp_bwd_kernel_events)
                     rc = go(2)
-                    marks[1].record()
-                    rnvp_bwd_kernel_events.append(marks)
+                    _mark_end(rnvp_bwd_kernel_events, marks)
                 if rc == _lib.MNF_OK:
                     rc = go(12)
             if rc != _lib.MNF_ERR_UNSUPPORTED:
@@ -733,7 +759,8 @@ def _linear_rows(lib, x: Tensor, W: Tensor, y: Tensor, force: int = 0, trans: bo
 
 
 def _linear_rows_image(lib, W: Tensor, table: Tensor) -> Tensor:
-    """W (dim, dim, contiguous) in the MFMA kernels' operand order: one small gather launch."""
+    """W (dim, dim, contiguous) in the MFMA kernels' operand order: one small gather launch.  (_HipFlow._packed gathers
+    a layer's flat parameters into its fp32 operand image by the same call.)"""
     img = torch.empty(table.numel(), dtype=torch.float32, device=W.device)
     _lib.check("mnf_pack_gather", lib.mnf_pack_gather(W.data_ptr(), table.data_ptr(), img.data_ptr(), table.numel(),
                                                       _stream()))
@@ -741,11 +768,8 @@ def _linear_rows_image(lib, W: Tensor, table: Tensor) -> Tensor:
 
 
 def _linear_rows_table(lib, dim: int, device) -> Tensor | None:
-    key = (dim, device)
-    if key not in _LINEAR_ROWS_INDEX:
-        idx = _counted_index(lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (dim,))
-        _LINEAR_ROWS_INDEX[key] = None if idx is None else _index_on(device, idx)
-    return _LINEAR_ROWS_INDEX[key]
+    return _device_table(_LINEAR_ROWS_INDEX, (dim, device), device, lambda: _counted_index(
+        lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (dim,)))
 
 
 _PAIR_FUSION_DIMS = (16, 32, 64)  # mnf_glow_actnorm_inv / _bwd (csrc/mnf_glow_actnorm.hip); other dims: _pair_route
@@ -1056,16 +1080,16 @@ class _AffineRunFn(torch.autograd.Function):
 
 
 class _HipFlow(nn.Module):
-    """Shared plumbing: packed-parameter caches keyed on parameter versions."""
+    """Shared plumbing: packed-parameter caches keyed on parameter versions, the per-device index tables, and the
+    layer-call frame (``_run``)."""
 
     def __init__(self) -> None:
         super().__init__()
         self._cache_key = None
         self._flat: Tensor | None = None
         self._image: Tensor | None = None
-        self._index: Tensor | None = None  # device int32 gather table, built once
         self._split: Tensor | None = None  # split (f16 hi + lo) operand image, see csrc/mnf_split.h
-        self._split_index = None           # (device int32 table, n_split_words, n_plain_words) or False
+        self.__dict__["_tables"] = {}      # name -> (device, index table(s)): _device_table
         self.force_generic = False  # tests: run the generic kernel even if an MFMA one exists
         self.force_fp32_mfma = False  # tests / MNF_FP32_MFMA=1: fp32 MFMA kernel instead of the split one
         # False: this conditioner always takes the fp32 MFMA kernels (set by layers whose hidden layers are so narrow
@@ -1093,9 +1117,6 @@ class _HipFlow(nn.Module):
         parameter's version counter, so after such a write call ``invalidate()`` (on the layer, or on the
         ``NormalizingFlow`` for all of its layers), or write with ``torch.no_grad(): p.clamp_()`` instead."""
         self._cache_key = None
-        for attr in ("_w_key", ):
-            if hasattr(self, attr):
-                setattr(self, attr, None)
 
     # subclasses: ordered parameter list == state_dict order
     def _packed_params(self) -> list[Tensor]:
@@ -1136,17 +1157,11 @@ class _HipFlow(nn.Module):
 
     def _device_index(self, device: torch.device) -> Tensor | None:
         """Device copy of the fp32 operand-image index table (built once), or None."""
-        if self._index is None or self._index.device != device:
-            host = self._image_index_host()
-            self._index = None if host is None else _index_on(device, host)
-        return self._index
+        return _device_table(self._tables, "image", device, self._image_index_host)
 
     def _device_split_index(self, device: torch.device):
         """(device index table, n_split_words, n_plain_words) of the split operand image, or False."""
-        if self._split_index is None or (self._split_index and self._split_index[0].device != device):
-            host = self._split_index_host()
-            self._split_index = False if host is None else (_index_on(device, host[0]), host[1], host[2])
-        return self._split_index
+        return _device_table(self._tables, "split", device, self._split_index_host) or False
 
     def _packed(self, device: torch.device, images: bool = True) -> tuple[Tensor | None, Tensor | None]:
         """(flat parameters, fp32 operand image) for the current parameter values.  ``images=False``: the caller's
@@ -1169,29 +1184,48 @@ class _HipFlow(nn.Module):
         elif _CHECK_PARAMS_EVERY:
             _check_params_fresh(params, self._flat, type(self).__name__)
         if images and self.__dict__.get("_images_key") != key:
-            self._device_index(device)
-            if self._index is not None:
-                image = torch.empty(self._index.numel(), dtype=torch.float32, device=device)
-                _lib.check("mnf_pack_gather", _lib.load().mnf_pack_gather(
-                    self._flat.data_ptr(), self._index.data_ptr(), image.data_ptr(),
-                    self._index.numel(), _stream()))
-                self._image = image
-            else:
-                self._image = None
-            self._device_split_index(device)
-            if self._split_index:
-                sidx, n_split, n_plain = self._split_index
-                split = torch.empty(n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32, device=device)
-                _lib.check("mnf_pack_gather_split", _lib.load().mnf_pack_gather_split(
-                    self._flat.data_ptr(), sidx.data_ptr(), split.data_ptr(), n_split, n_plain, _stream()))
-                self._split = split
-            else:
-                self._split = None
+            lib = _lib.load()
+            index, split_index = self._device_index(device), self._device_split_index(device)
+            self._image = None if index is None else _linear_rows_image(lib, self._flat, index)
+            self._split = _pack_split(lib, self._flat, split_index) if split_index else None
             self.__dict__["_images_key"] = key
         return self._flat, self._image
 
+    # ---- the layer-call frame.  A layer supplies _train (gradients wanted: the flat stand-in and its autograd Function)
+    # and _plain (one launch on validated buffers); RNVP, AffineConstantFlow and Glow, whose ordering and log-det shapes
+    # differ, keep bodies of their own on the same pieces (_trains, _checked, _outputs).
+    def _trains(self, x, accum: Tensor | None) -> bool:
+        """Does this call take the autograd path?  (Never with ``accum``: the kernel adds log_det in place there.)"""
+        return accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x)
+
+    def _checked(self, x, grad: bool = False) -> Tensor:
+        """The validated (rows, self.dim) input: detached, or with its autograd link (``grad``)."""
+        x = _grad_input(x) if grad else _device_input(x, "input")
+        if x.shape[1] != self.dim:
+            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
+        return x
+
     # out-of-place layer on raw buffers; accum: (rows,) tensor receiving ``+= log_det`` or None
     def _run(self, x: Tensor, inverse: bool, accum: Tensor | None) -> tuple[Tensor, Tensor | None]:
+        return self._call(x, inverse, accum, True, int(accum is not None))
+
+    def _call(self, x, inverse, accum, may_train: bool, accumulate: int, *extra):
+        """The frame proper; ``extra``: what a layer's own ``_run`` keywords hand on to its ``_plain``."""
+        if may_train and self._trains(x, accum):
+            return self._train(x, bool(inverse))
+        x = self._checked(x)
+        if x.shape[0] == 0:
+            return _empty_result(x, accum)
+        y, ld = _outputs(x, accum)
+        self._plain(x, y, ld, accumulate, bool(inverse), *extra)
+        return y, (None if accum is not None else ld)
+
+    def _train(self, x, inverse: bool):
+        """(y, log_det) with gradients: ``self._checked(x, grad=True)``, the flat stand-in, the autograd Function."""
+        raise NotImplementedError
+
+    def _plain(self, x: Tensor, y: Tensor, ld: Tensor, accumulate: int, inverse: bool) -> None:
+        """One launch without gradients: y written, log_det written to (or, ``accumulate``, added to) ``ld``."""
         raise NotImplementedError
 
 
@@ -1239,12 +1273,8 @@ class AffineHalfFlow(_TwoWayFlow):
     def _bwd_split_index(self, device):
         """(device index table, n_split_words, n_plain_words) of the split gradient kernel's operand image (forward
         and transposed weights), built once per module; False: no such kernel for this shape."""
-        cached = self.__dict__.get("_bwd_split_index_cache")
-        if cached is None or (cached and cached[0].device != device):
-            host = _layout_index(_lib.load(), "mnf_affine_half_bwd_split", self._shape())
-            cached = False if host is None else (_index_on(device, host[0]), host[1], host[2])
-            self.__dict__["_bwd_split_index_cache"] = cached
-        return cached
+        return _device_table(self._tables, "bwd_split", device, lambda: _layout_index(
+            _lib.load(), "mnf_affine_half_bwd_split", self._shape())) or False
 
     def _bwd_split_ok(self) -> bool:
         return not (self.force_fp32_mfma or _FP32_MFMA_ENV or _dispatch.BWD_FP32 or self.force_generic or not self._split_ok)
@@ -1255,52 +1285,40 @@ class AffineHalfFlow(_TwoWayFlow):
         if not self._bwd_split_ok():
             return None
         table = self._bwd_split_index(device)
-        if not table:
-            return None
-        idx, n_split, n_plain = table
-        image = torch.empty(n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32, device=device)
-        _lib.check("mnf_pack_gather_split", _lib.load().mnf_pack_gather_split(
-            flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, n_plain, _stream()))
-        return image
+        return _pack_split(_lib.load(), flat, table) if table else None
 
     def _bwd_index(self, device) -> Tensor | None:
         """Device index table of the MFMA gradient kernel (built once per module), or None."""
-        cached = self.__dict__.get("_bwd_index_cache")
-        if cached is None or (cached[0] is not None and cached[0].device != device):
-            idx = _counted_index(_lib.load(), "mnf_affine_half_bwd_index_ints", "mnf_affine_half_bwd_index", self._shape())
-            cached = (None if idx is None else _index_on(device, idx),)
-            self.__dict__["_bwd_index_cache"] = cached
-        return cached[0]
+        return _device_table(self._tables, "bwd", device, lambda: _counted_index(
+            _lib.load(), "mnf_affine_half_bwd_index_ints", "mnf_affine_half_bwd_index", self._shape()))
 
     def _split_index_host(self):
         return _layout_index(_lib.load(), "mnf_affine_half_split", self._shape())
 
     def _run(self, x, inverse, accum, sqnorm: Tensor | None = None, overwrite: bool = False):
         # overwrite: accum receives ld instead of += ld (first layer of a pass: saves zero-filling it)
-        if accum is None and sqnorm is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 \
-                and _wants_grad(self, x):
-            xg = _grad_input(x)
-            if xg.shape[1] != self.dim:
-                raise ValueError(f"expected dim {self.dim}, got {xg.shape[1]}")
-            params = self._packed_params()
-            flat = torch.cat([p.reshape(-1) for p in params]) if params else xg.new_empty(0)
-            return _AffineHalfFn.apply(xg, flat, self, bool(inverse))
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        if x.shape[0] == 0:
-            return _empty_result(x, accum)
+        return self._call(x, inverse, accum, sqnorm is None, int(accum is not None and not overwrite), sqnorm)
+
+    def _train(self, x, inverse):
+        xg = self._checked(x, grad=True)
+        params = self._packed_params()
+        flat = torch.cat([p.reshape(-1) for p in params]) if params else xg.new_empty(0)
+        return _AffineHalfFn.apply(xg, flat, self, inverse)
+
+    def _forward_launch(self, x, y, ld, accumulate, inverse, sqnorm) -> Tensor | None:
+        """THE forward launch (mnf_affine_half_sq; ``sqnorm`` None: no |y_row|^2), for _plain and _AffineHalfFn.forward
+        alike; returns the flat parameters it ran on."""
         flat, image, split = self._packed3(x.device)
-        y = torch.empty_like(x)
-        ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
         _lib.check("mnf_affine_half_sq", _lib.load().mnf_affine_half_sq(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), _ptr(sqnorm), int(accum is not None and not overwrite),
-            _ptr(flat), _ptr(image), _ptr(split), x.shape[0], self.dim, int(bool(self.parity)),
-            int(inverse), len(self.h_sizes),
-            self._hid, int(self.scale), int(self.shift), self._force_code(image), _stream()))
+            x.data_ptr(), y.data_ptr(), ld.data_ptr(), _ptr(sqnorm), accumulate, _ptr(flat), _ptr(image), _ptr(split),
+            x.shape[0], self.dim, int(bool(self.parity)), int(inverse), len(self.h_sizes), self._hid, int(self.scale),
+            int(self.shift), self._force_code(image), _stream()))
+        return flat
+
+    def _plain(self, x, y, ld, accumulate, inverse, sqnorm=None):
+        self._forward_launch(x, y, ld, accumulate, inverse, sqnorm)
         if not self.force_generic:
             _lib.note_generic("AffineHalfFlow", x.shape[0], f"dim={self.dim}, hidden={self.h_sizes}")
-        return y, (None if accum is not None else ld)
 
     def emits_sqnorm(self, device, rows: int | None = None) -> bool:
         """True when this layer's kernel can also write |y_row|^2: the specialised kernels (a half narrower than its
@@ -1352,22 +1370,21 @@ class NSF_CL(_TwoWayFlow):
     def _bwd_tile_tables(self, device):
         """(operand index table, flush table, n_split_words, n_plain_words) of the tile gradient kernel on the device,
         built once per module; False: no such kernel for this shape."""
-        cached = self.__dict__.get("_bwd_tile_cache")
-        if cached is None or (cached and cached[0].device != device):
+        def host():
             lib = _lib.load()
             n_split, n_plain, n_params = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
             rc = lib.mnf_nsf_cl_bwd_tile_layout(self.dim, self.K, len(self.h_sizes), self._hid, ctypes.byref(n_split),
                                                 ctypes.byref(n_plain), ctypes.byref(n_params))
-            cached = False
-            if rc != _lib.MNF_ERR_UNSUPPORTED:
-                _lib.check("mnf_nsf_cl_bwd_tile_layout", rc)
-                idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-                flush = (ctypes.c_int32 * n_params.value)()
-                _lib.check("mnf_nsf_cl_bwd_tile_index", lib.mnf_nsf_cl_bwd_tile_index(
-                    self.dim, self.K, len(self.h_sizes), self._hid, idx, flush))
-                cached = (_index_on(device, idx), _index_on(device, flush), n_split.value, n_plain.value)
-            self.__dict__["_bwd_tile_cache"] = cached
-        return cached
+            if rc == _lib.MNF_ERR_UNSUPPORTED:
+                return None
+            _lib.check("mnf_nsf_cl_bwd_tile_layout", rc)
+            idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
+            flush = (ctypes.c_int32 * n_params.value)()
+            _lib.check("mnf_nsf_cl_bwd_tile_index", lib.mnf_nsf_cl_bwd_tile_index(
+                self.dim, self.K, len(self.h_sizes), self._hid, idx, flush))
+            return idx, flush, n_split.value, n_plain.value
+
+        return _device_table(self._tables, "bwd_tile", device, host) or False
 
     # ---- halves that are not whole float4 groups (dim = 2, 4, 6, 10, ...; the reference's own test shape is dim = 2,
     # tests/test_flows.py:89-99).  The matrix-core kernels take halves in whole groups of four columns, so such a layer
@@ -1428,7 +1445,7 @@ class NSF_CL(_TwoWayFlow):
         twin = self._twin(x.device, hp)
         fill = x.new_full((rows, hp - hr), 2.0 * float(self.B) + 1.0)  # outside [-B, B]: identity, log-derivative 0
         wants = accum is None and _wants_grad(self, x)
-        xs = _grad_input(x) if wants else _device_input(x, "input")
+        xs = self._checked(x, grad=wants)
         x_pad = torch.cat([xs[:, :hr], fill, xs[:, hr:], fill], dim=1)
         if wants:
             flat_pad = torch.cat([q.reshape(-1) for q in self._padded_params(hp)])
@@ -1444,28 +1461,24 @@ class NSF_CL(_TwoWayFlow):
             hp = self._pad_half()
             if hp:
                 return self._run_padded(x, inverse, accum, hp)
-        if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
-            xg = _grad_input(x)
-            if xg.shape[1] != self.dim:
-                raise ValueError(f"expected dim {self.dim}, got {xg.shape[1]}")
-            flat = torch.cat([p.reshape(-1) for p in self._packed_params()])
-            return _NsfFn.apply(xg, flat, self, bool(inverse))
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        if x.shape[0] == 0:
-            return _empty_result(x, accum)
+        return super()._run(x, inverse, accum)
+
+    def _train(self, x, inverse):
+        xg = self._checked(x, grad=True)
+        return _NsfFn.apply(xg, torch.cat([p.reshape(-1) for p in self._packed_params()]), self, inverse)
+
+    def _forward_launch(self, x, y, ld, accumulate, inverse) -> Tensor:
+        """THE forward launch (mnf_nsf_cl), for _plain and _NsfFn.forward alike; returns the flat parameters it ran on."""
         flat, image, split = self._packed3(x.device)
-        y = torch.empty_like(x)
-        ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
         _lib.check("mnf_nsf_cl", _lib.load().mnf_nsf_cl(
-            x.data_ptr(), y.data_ptr(), ld.data_ptr(), int(accum is not None), _ptr(flat), _ptr(image),
-            _ptr(split),
-            x.shape[0], self.dim, self.K, float(self.B), int(inverse), len(self.h_sizes), self._hid,
-            self._force_code(image), _stream()))
+            x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, _ptr(flat), _ptr(image), _ptr(split), x.shape[0],
+            self.dim, self.K, float(self.B), int(inverse), len(self.h_sizes), self._hid, self._force_code(image),
+            _stream()))
         if not self.force_generic and not self._pad_half():  # (a padded-twin shape is here by choice: few rows)
             _lib.note_generic("NSF_CL", x.shape[0], f"dim={self.dim}, K={self.K}, hidden={self.h_sizes}")
-        return y, (None if accum is not None else ld)
+        return flat
+
+    _plain = _forward_launch
 
 
 class _NsfArFn(torch.autograd.Function):
@@ -1475,8 +1488,7 @@ class _NsfArFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, flat_with_grad, module, inverse):
         flat = flat_with_grad.detach().contiguous()
-        y = torch.empty_like(x)
-        ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        y, ld = _outputs(x, None)
         module._launch(x, y, ld, 0, flat, inverse)
         ctx.module, ctx.inverse = module, inverse
         ctx.save_for_backward(x, flat)
@@ -1580,23 +1592,12 @@ class NSF_AR(_TwoWayFlow):
             x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), rows, self.dim, self.K, float(self.B),
             int(inverse), len(self.h_sizes), self._hid, _stream()))
 
-    def _run(self, x, inverse, accum):
-        if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
-            xg = _grad_input(x)
-            if xg.shape[1] != self.dim:
-                raise ValueError(f"expected dim {self.dim}, got {xg.shape[1]}")
-            flat = torch.cat([p.reshape(-1) for p in self._packed_params()])
-            return _NsfArFn.apply(xg, flat, self, bool(inverse))
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        if x.shape[0] == 0:
-            return _empty_result(x, accum)
-        flat, _ = self._packed(x.device)
-        y = torch.empty_like(x)
-        ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        self._launch(x, y, ld, int(accum is not None), flat, bool(inverse))
-        return y, (None if accum is not None else ld)
+    def _train(self, x, inverse):
+        xg = self._checked(x, grad=True)
+        return _NsfArFn.apply(xg, torch.cat([p.reshape(-1) for p in self._packed_params()]), self, inverse)
+
+    def _plain(self, x, y, ld, accumulate, inverse):
+        self._launch(x, y, ld, accumulate, self._packed(x.device)[0], inverse)
 
 
 def rqs(inputs: Tensor, W: Tensor, H: Tensor, D: Tensor, inverse: bool = False,
@@ -1651,12 +1652,8 @@ class RNVP(_HipFlow):
 
     def _bwd_index(self, device):
         """(device index table, n_split_words, n_plain_words) of the gradient kernels' operand image, or False."""
-        cached = self.__dict__.get("_bwd_idx")
-        if cached is None or (cached and cached[0].device != device):
-            host = _layout_index(_lib.load(), "mnf_rnvp_bwd_mfma", (self.dim, len(self.h_sizes), self._hid))
-            cached = False if host is None else (_index_on(device, host[0]), host[1], host[2])
-            self.__dict__["_bwd_idx"] = cached
-        return cached
+        return _device_table(self._tables, "bwd", device, lambda: _layout_index(
+            _lib.load(), "mnf_rnvp_bwd_mfma", (self.dim, len(self.h_sizes), self._hid))) or False
 
     def _bwd_image(self, device, flat: Tensor) -> Tensor | None:
         """The gradient kernels' operand image for the parameters in ``flat`` (repacked per backward pass: the weights
@@ -1666,7 +1663,6 @@ class RNVP(_HipFlow):
         table = self._bwd_index(device)
         if not table:
             return None
-        idx, n_split, n_plain = table
         # one pack per parameter state: `flat` is the forward pass's packed-parameter tensor (replaced, never rewritten,
         # when a parameter changes), and a layer is differentiated several times per step (MNF: sample_z in forward
         # and again in kl_div)
@@ -1674,9 +1670,7 @@ class RNVP(_HipFlow):
         capturing = torch.cuda.is_current_stream_capturing()
         if cached is not None and cached[0] is flat and cached[1] == (flat._version, capturing):
             return cached[2]
-        image = torch.empty(n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32, device=device)
-        _lib.check("mnf_pack_gather_split", _lib.load().mnf_pack_gather_split(
-            flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, n_plain, _stream()))
+        image = _pack_split(_lib.load(), flat, table)
         self.__dict__["_bwd_img"] = (flat, (flat._version, capturing), image)
         return image
 
@@ -1715,11 +1709,9 @@ class RNVP(_HipFlow):
         inside the kernel (MNFLinear.sample_z); returns None when that fused form is not available."""
         if inverse:
             raise AttributeError("RNVP has no inverse (flows/rnvp.py defines forward only)")
-        want_grad = accum is None and isinstance(z, Tensor) and z.is_cuda and z.shape[0] > 0 and _wants_grad(self, z)
+        want_grad = self._trains(z, accum)
         zin = z
-        z = _device_input(z, "input")
-        if z.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {z.shape[1]}")
+        z = self._checked(z)
         if z.shape[0] == 0:
             return _empty_result(z, accum)
         if mask is not None:
@@ -1737,15 +1729,14 @@ class RNVP(_HipFlow):
         if want_grad:
             params = self._packed_params()
             home = _flat_home_of(self, params)
-            flat_g = _home_stand_in(self, z.device) if home is not None else torch.cat([p.reshape(-1) for p in params])
-            return _RnvpFn.apply(_grad_input(zin), flat_g, self, mask, int(seed or 0) & 0xFFFFFFFFFFFFFFFF, home)
+            return _RnvpFn.apply(_grad_input(zin), _flat_input(self, params, home, z.device), self, mask,
+                                 int(seed or 0) & 0xFFFFFFFFFFFFFFFF, home)
         few = prologue is None and self._few(z.shape[0], mask is not None)
         if few:
             flat, image, split = self._packed(z.device, images=False)[0], None, None
         else:
             flat, image, split = self._packed3(z.device)
-        x = torch.empty_like(z)
-        ld = accum if accum is not None else torch.empty(z.shape[0], dtype=torch.float32, device=z.device)
+        x, ld = _outputs(z, accum)
         if prologue is not None:
             if image is None or split is None or self.force_generic:
                 return None
@@ -1779,8 +1770,7 @@ class _MafFn(torch.autograd.Function):
     def forward(ctx, x, flat_with_grad, module, sequential, home=None):
         flat, _ = module._packed(x.device)
         masks = module._mask_bytes(x.device)
-        y = torch.empty_like(x)
-        ld = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        y, ld = _outputs(x, None)
         module._launch(x, y, ld, 0, flat, masks, sequential)
         ctx.module, ctx.sequential, ctx.home = module, sequential, home
         ctx.save_for_backward(x, y, flat, masks)
@@ -1924,37 +1914,26 @@ class MAF(_TwoWayFlow):
             x.data_ptr(), y.data_ptr(), ld.data_ptr(), accumulate, flat.data_ptr(), masks.data_ptr(), rows, self.dim,
             int(bool(self.parity)), int(sequential), len(self.h_sizes), self._hid, _stream()))
 
-    def _run(self, x, inverse, accum):
-        sequential = bool(inverse) != self._sequential_forward
-        if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
-            if sequential and not self._autoregressive_in_index_order():
-                # mnf_maf_bwd evaluates the network ONCE on the decoded output and reuses those activations for every
-                # step of the element-by-element pass: right only when element i never sees elements >= i, i.e. for
-                # masks that are autoregressive in index order.  With any other MADE (natural_ordering=False, several
-                # masks, masks from a state_dict) the VALUES of this direction still match the reference (flows/maf.py:
-                # 39-50: elements not yet decoded are zero at step i), its gradients would not.
-                raise NotImplementedError(
-                    f"{type(self).__name__}: gradients of the element-by-element direction need a MADE whose masks are "
-                    f"autoregressive in index order (MADE(..., natural_ordering=True)); the one-pass direction and both "
-                    f"directions' values work with any MADE")
-            xg = _grad_input(x)
-            if xg.shape[1] != self.dim:
-                raise ValueError(f"expected dim {self.dim}, got {xg.shape[1]}")
-            params = self._packed_params()
-            home = _flat_home_of(self, params)
-            flat = _home_stand_in(self, xg.device) if home is not None else torch.cat([p.reshape(-1) for p in params])
-            return _MafFn.apply(xg, flat, self, sequential, home)
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        if x.shape[0] == 0:
-            return _empty_result(x, accum)
-        flat, _ = self._packed(x.device)
-        masks = self._mask_bytes(x.device)
-        y = torch.empty_like(x)
-        ld = accum if accum is not None else torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-        self._launch(x, y, ld, int(accum is not None), flat, masks, sequential)
-        return y, (None if accum is not None else ld)
+    def _train(self, x, inverse):
+        sequential = inverse != self._sequential_forward
+        if sequential and not self._autoregressive_in_index_order():
+            # mnf_maf_bwd evaluates the network ONCE on the decoded output and reuses those activations for every
+            # step of the element-by-element pass: right only when element i never sees elements >= i, i.e. for
+            # masks that are autoregressive in index order.  With any other MADE (natural_ordering=False, several
+            # masks, masks from a state_dict) the VALUES of this direction still match the reference (flows/maf.py:
+            # 39-50: elements not yet decoded are zero at step i), its gradients would not.
+            raise NotImplementedError(
+                f"{type(self).__name__}: gradients of the element-by-element direction need a MADE whose masks are "
+                f"autoregressive in index order (MADE(..., natural_ordering=True)); the one-pass direction and both "
+                f"directions' values work with any MADE")
+        xg = self._checked(x, grad=True)
+        params = self._packed_params()
+        home = _flat_home_of(self, params)
+        return _MafFn.apply(xg, _flat_input(self, params, home, xg.device), self, sequential, home)
+
+    def _plain(self, x, y, ld, accumulate, inverse):
+        self._launch(x, y, ld, accumulate, self._packed(x.device)[0], self._mask_bytes(x.device),
+                     inverse != self._sequential_forward)
 
 
 class IAF(MAF):
@@ -1981,14 +1960,12 @@ class AffineConstantFlow(_TwoWayFlow):
             self.register_buffer("t", torch.zeros(1, dim), persistent=False)
 
     def _run(self, x, inverse, accum):
-        if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
+        if self._trains(x, accum):
             xg = _grad_input(x)
             y = _AffineConstFn.apply(xg, self.s.to(xg.device), self.t.to(xg.device), bool(inverse))
             return y, torch.sum(-self.s if inverse else self.s, dim=1).to(xg.device)
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        s = self.s.detach().to(x.device, torch.float32).contiguous()
+        x = self._checked(x)
+        s =self.s.detach().to(x.device, torch.float32).contiguous()
         t = self.t.detach().to(x.device, torch.float32).contiguous()
         if x.shape[0] == 0:
             ld1 = (-s if inverse else s).sum(dim=1)
@@ -2104,7 +2081,10 @@ class Glow(_TwoWayFlow):
         self._w_inv: Tensor | None = None
         self._w_ld: Tensor | None = None      # sum(log|S|), cached with W
         self._w_img: dict = {}                # inverse? -> MFMA operand image of W / W^-1
-        self._w_index: Tensor | None = None
+
+    def invalidate(self) -> None:
+        super().invalidate()
+        self._w_key = None
 
     def _P_on(self, device) -> Tensor:
         """``P`` on ``device`` (P is a plain attribute -- it does not follow ``.to()`` -- so it may live on the host:
@@ -2163,21 +2143,12 @@ class Glow(_TwoWayFlow):
         W = self._weights(device, inverse)
         if inverse not in self._w_img:
             lib = _lib.load()
-            n = lib.mnf_linear_rows_image_floats(self.dim)
-            if n <= 0 or self.force_generic:
-                self._w_img[inverse] = None
-            else:
-                if self._w_index is None or self._w_index.device != device:
-                    self._w_index = _index_on(device, _counted_index(
-                        lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (self.dim,)))
-                img = torch.empty(n, dtype=torch.float32, device=device)
-                _lib.check("mnf_pack_gather", lib.mnf_pack_gather(
-                    W.data_ptr(), self._w_index.data_ptr(), img.data_ptr(), n, _stream()))
-                self._w_img[inverse] = img
+            table = None if self.force_generic else _linear_rows_table(lib, self.dim, device)
+            self._w_img[inverse] = None if table is None else _linear_rows_image(lib, W, table)
         return self._w_img[inverse]
 
     def _run(self, x, inverse, accum):
-        if accum is None and isinstance(x, Tensor) and x.is_cuda and x.shape[0] > 0 and _wants_grad(self, x):
+        if self._trains(x, accum):
             xg = _grad_input(x)
             if (self.dim <= _GLOW_WEIGHT_MAX_DIM and self.L.is_cuda and self.L.device == xg.device
                     and self.L.dtype == torch.float32):
@@ -2197,10 +2168,8 @@ class Glow(_TwoWayFlow):
                 return (_LinearRowsFn.apply(xg, torch.linalg.inv_ex(W).inverse.to(xg.device), int(self.force_generic)),
                         -ld.to(xg.device))
             return _LinearRowsFn.apply(xg, W.to(xg.device), int(self.force_generic)), ld.to(xg.device)
-        x = _device_input(x, "input")
-        if x.shape[1] != self.dim:
-            raise ValueError(f"expected dim {self.dim}, got {x.shape[1]}")
-        W = self._weights(x.device, inverse)
+        x = self._checked(x)
+        W =self._weights(x.device, inverse)
         y = torch.empty_like(x)
         if x.shape[0] > 0:
             route = _dispatch.glow_route(x.shape[0], self.dim, int(self.force_generic))
@@ -2231,7 +2200,6 @@ class _SplineBlockRun:
         self.dim = nsf.dim
         self._aff_key = None
         self._aff: dict = {}
-        self._lin_index: Tensor | None = None
         self._unsupported = False
 
     def _affine(self, device, inverse: bool):
@@ -2246,8 +2214,8 @@ class _SplineBlockRun:
             _check_params_fresh((an.s, an.t, gl.L, gl.S, gl.U), self.__dict__.get("_aff_from"), "an [ActNorm, Glow] block")
         if inverse not in self._aff:
             lib = _lib.load()
-            n = lib.mnf_linear_rows_image_floats(self.dim)
-            if n <= 0:
+            table = _linear_rows_table(lib, self.dim, device)
+            if table is None:
                 self._aff[inverse] = None
                 return None
             s = an.s.detach().to(device, torch.float32).reshape(-1)
@@ -2259,13 +2227,7 @@ class _SplineBlockRun:
             else:         # x = (z e^s + t) @ W
                 A, b = torch.exp(s)[:, None] * W, t @ W
                 ldc = s.sum() + gl._w_ld
-            if self._lin_index is None or self._lin_index.device != device:
-                self._lin_index = _index_on(device, _counted_index(
-                    lib, "mnf_linear_rows_image_floats", "mnf_linear_rows_image_index", (self.dim,)))
-            aff = torch.empty(n + self.dim, dtype=torch.float32, device=device)
-            _lib.check("mnf_pack_gather", lib.mnf_pack_gather(
-                A.contiguous().data_ptr(), self._lin_index.data_ptr(), aff.data_ptr(), n, _stream()))
-            aff[n:] = b
+            aff = torch.cat((_linear_rows_image(lib, A.contiguous(), table), b))
             scale_shift = torch.cat((torch.exp(s), t)).contiguous()
             self._aff[inverse] = (aff, float(ldc), scale_shift)  # one host read per parameter update
         return self._aff[inverse]
@@ -2378,7 +2340,6 @@ class _AffineRun:
         self._flat_checked = None
         self._grad_i0 = None     # index of the run's first parameter in FlatParameters.params
         self._home_now = None    # the flat home of the call in flight (set by launch_grad, read by _AffineRunFn)
-        self._stand_in = None
         self._rt_key = None      # the run-time-shaped route: key and tensor of the concatenated parameters
         self._rt_flat: Tensor | None = None
         self._rt_shape_ok = None  # mnf_affine_half_rt_stack_supported, asked once
@@ -2465,12 +2426,7 @@ class _AffineRun:
                     flat.data_ptr(), index.data_ptr(), self._images.data_ptr(), index.numel(), n, stride, _stream()))
                 sidx = f0._device_split_index(device)
                 if sidx and not _FP32_MFMA_ENV and not any(f.force_fp32_mfma or not f._split_ok for f in self.layers):
-                    table, n_split, n_plain = sidx
-                    self._splits = torch.empty(n * (n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS), dtype=torch.int32,
-                                               device=device)
-                    _lib.check("mnf_pack_gather_split_batch", lib.mnf_pack_gather_split_batch(
-                        flat.data_ptr(), table.data_ptr(), self._splits.data_ptr(), n_split, n_plain, n, stride,
-                        _stream()))
+                    self._splits = _pack_split(lib, flat, sidx, n, stride)
                 # (debug switch MNF_CHECK_PARAMS: keep what the images were packed from -- with a flat home `flat` is
                 #  the live buffer itself, so a copy)
                 self._packed_from = flat.detach().clone() if _CHECK_PARAMS_EVERY else None
@@ -2489,12 +2445,8 @@ class _AffineRun:
         table = f0._bwd_split_index(device)
         if not table:
             return None
-        idx, n_split, n_plain = table
-        words = n_split + n_plain + _lib.MNF_SPLIT_TAIL_WORDS
-        images = torch.empty(n * words, dtype=torch.int32, device=device)
-        _lib.check("mnf_pack_gather_split_batch", _lib.load().mnf_pack_gather_split_batch(
-            flat.data_ptr(), idx.data_ptr(), images.data_ptr(), n_split, n_plain, n, flat.numel() // n, _stream()))
-        return images, words
+        images = _pack_split(_lib.load(), flat, table, n, flat.numel() // n)
+        return images, images.numel() // n
 
     def rt_route(self, rows: int, device) -> bool:
         """True when a no-grad pass of ``rows`` rows goes out as ONE launch of the run-time-shaped kernel
@@ -2592,12 +2544,7 @@ class _AffineRun:
             return None
         self._home_now = self.flat_home()
         self._rt_now = not self._per_shape_trainable(x.device) and self.rt_train_route(x.shape[0], x.device)
-        if self._home_now is not None:
-            if self._stand_in is None or self._stand_in.device != x.device:
-                self._stand_in = torch.zeros(1, device=x.device, requires_grad=True)
-            flat = self._stand_in
-        else:
-            flat = torch.cat([p.reshape(-1) for p in self._params()])
+        flat = _flat_input(self, self._params, self._home_now, x.device)
         try:
             out = _AffineRunFn.apply(_grad_input(x), flat, self, bool(inverse), bool(with_lp))
         except MnfHipError as err:  # an image exists but no stack kernel (e.g. hidden width 32): layer by layer

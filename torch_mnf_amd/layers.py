@@ -10,7 +10,6 @@ term of the reference's formula in one launch each way (``mnf_mnf_kl_fwd`` / ``_
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 
@@ -73,10 +72,7 @@ class _MnfLinearFn(torch.autograd.Function):
         lib = _lib.load()
         rows, dev = xc.shape[0], xc.device
         g = grad_out.contiguous()
-        idx, n_split = m._bwd_index(dev)
-        image = torch.empty(n_split + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32, device=dev)
-        _lib.check("mnf_pack_gather_split", lib.mnf_pack_gather_split(
-            flat.data_ptr(), idx.data_ptr(), image.data_ptr(), n_split, 0, _stream()))
+        image = _flows._pack_split(lib, flat, (*m._bwd_index(dev), 0))
         need = int(lib.mnf_mnf_linear_bwd_workspace_bytes(rows, m.n_in, m.n_out))
         key = (dev, _stream())
         work = _MNF_LINEAR_BWD_WORK.get(key)
@@ -485,18 +481,11 @@ class MNFLinear(nn.Module):
         cache = self.__dict__.get("_fwd_cache")
         if cache is None or cache[0] != key:
             lib = _lib.load()
-            n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-            rc = lib.mnf_mnf_linear_split_layout(self.n_in, self.n_out, ctypes.byref(n_split), ctypes.byref(n_plain))
-            if rc == _lib.MNF_ERR_UNSUPPORTED:
+            table = _flows._device_table(self.__dict__.setdefault("_tables", {}), "fwd", device, lambda: _flows._layout_index(
+                lib, "mnf_mnf_linear_split", (self.n_in, self.n_out)))
+            if table is None:
                 cache = (key, None)
             else:
-                _lib.check("mnf_mnf_linear_split_layout", rc)
-                index = self.__dict__.get("_fwd_index")
-                if index is None or index.device != device:
-                    idx = (ctypes.c_int32 * (2 * n_split.value + n_plain.value))()
-                    _lib.check("mnf_mnf_linear_split_index", lib.mnf_mnf_linear_split_index(self.n_in, self.n_out, idx))
-                    index = torch.frombuffer(idx, dtype=torch.int32).clone().to(device)
-                    self.__dict__["_fwd_index"] = index
                 with torch.no_grad():
                     w_var = self.W_log_var.detach().to(device, torch.float32).exp()
                     # exp(W_log_var) is ~1e-4 at init and shrinks in training: times a power of two that puts its
@@ -517,11 +506,7 @@ class MNFLinear(nn.Module):
                                       (w_var * (2.0 ** shift)).reshape(-1),
                                       self.b_mean.detach().to(device, torch.float32),
                                       self.b_log_var.detach().to(device, torch.float32).exp()]).contiguous()
-                image = torch.empty(n_split.value + n_plain.value + _lib.MNF_SPLIT_TAIL_WORDS, dtype=torch.int32,
-                                    device=device)
-                _lib.check("mnf_pack_gather_split", lib.mnf_pack_gather_split(
-                    flat.data_ptr(), index.data_ptr(), image.data_ptr(), n_split.value, n_plain.value, _stream()))
-                cache = (key, (flat, image, 2.0 ** -shift))
+                cache = (key, (flat, _flows._pack_split(lib, flat, table), 2.0 ** -shift))
                 if _flows._CHECK_PARAMS_EVERY:  # debug switch: the raw parameters the image was packed from
                     self.__dict__["_fwd_packed_from"] = torch.cat([p.detach().reshape(-1) for p in params]).clone()
             self.__dict__["_fwd_cache"] = cache
@@ -531,17 +516,11 @@ class MNFLinear(nn.Module):
 
     def _bwd_index(self, device):
         """(device index table, n_split_words) of the gradient kernels' operand image."""
-        cached = self.__dict__.get("_bwd_idx")
-        if cached is None or cached[0].device != device:
-            lib = _lib.load()
-            n_split, n_plain = ctypes.c_int64(0), ctypes.c_int64(0)
-            _lib.check("mnf_mnf_linear_bwd_layout", lib.mnf_mnf_linear_bwd_layout(
-                self.n_in, self.n_out, ctypes.byref(n_split), ctypes.byref(n_plain)))
-            idx = (ctypes.c_int32 * (2 * n_split.value))()
-            _lib.check("mnf_mnf_linear_bwd_index", lib.mnf_mnf_linear_bwd_index(self.n_in, self.n_out, idx))
-            cached = (torch.frombuffer(idx, dtype=torch.int32).clone().to(device), n_split.value)
-            self.__dict__["_bwd_idx"] = cached
-        return cached
+        table = _flows._device_table(self.__dict__.setdefault("_tables", {}), "bwd", device, lambda: _flows._layout_index(
+            _lib.load(), "mnf_mnf_linear_bwd", (self.n_in, self.n_out)))
+        if table is None:
+            _lib.check("mnf_mnf_linear_bwd_layout", _lib.MNF_ERR_UNSUPPORTED)
+        return table[:2]
 
     def forward(self, x: Tensor, eps: Tensor | None = None) -> Tensor:
         """Algorithm 1 of the MNF paper (mnf_linear.py:46-56): ``mean + sqrt(var) * eps`` with
