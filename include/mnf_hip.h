@@ -139,6 +139,12 @@ int mnf_affine_half_sq(const float* x, float* y, float* log_det, float* y_sqnorm
  * log_prob (rows,) / log_prob_sum (device double, ADDED to; caller zeroes it), both optional (split kernel only,
  * need log_det): the standard-normal base log-prob epilogue log_det - |y|^2/2 - dim/2 log(2 pi) of
  * mnf_gauss_logprob fused into the same launch (when the stack is the whole inverse pass of a model).
+ * y == NULL: a density-only launch, which writes no row tensor (4*dim bytes per row in, log_det and what the consumer
+ * takes out).  Allowed exactly when intermediates == NULL, log_det != NULL (required and written as ever) and at least
+ * one of y_sqnorm, log_prob, log_prob_sum is given -- something that consumes the rows inside the kernel; any other
+ * call with y == NULL is MNF_ERR_INVALID_ARG before a launch.  log_det, y_sqnorm, log_prob and the sum are bit for
+ * bit those of the same call with y.  Both kernels take it (with y_sqnorm alone the fp32 kernel too: the separate
+ * mnf_gauss_logprob_sq epilogue reads only y_sqnorm and log_det).
  * MNF_ERR_UNSUPPORTED for shapes without a fused kernel: the split kernel covers every shape that has a split image
  * except hidden width 32 at full-tile dim <= 64 with n_layers > 1 (no faster than one launch per layer); the fp32
  * kernel behind it dim in {32, 64} with hidden width 24 or 16. */

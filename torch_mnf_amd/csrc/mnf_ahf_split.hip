@@ -196,6 +196,8 @@ ahf_split_kernel(const float* __restrict__ x, float* __restrict__ y, float* __re
 // a double buffer while the current layer computes; one barrier per layer.
 // mid != nullptr: the output of every layer but the last goes to mid[li] (application order): each
 // intermediate tensor is written once and never re-read.
+// y == nullptr (only with mid == nullptr and ysq / log_prob / log_prob_sum, see mnf_affine_half_stack): no row is
+// written at all -- the launch reads x and writes 8 bytes per row.
 // ------------------------------------------------------------------------------------------------
 // d <= 64: two row tiles per wave (shared operand reads), four waves, two workgroups per CU.
 // d >= 128: the rows of ONE tile already take 32-64 VGPRs and the double-buffered image 90-150 KB of LDS:
@@ -398,7 +400,7 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
     }
 #pragma unroll
     for (int t = 0; t < NTL; ++t) {
-      if (live[t]) {
+      if (live[t] && y != nullptr) {  // y == nullptr: a density-only launch, the rows end in sq / lp below
         float* yr = y + rowc[t] * dim;
 #pragma unroll
         for (int g = 0; g < G; ++g) half_store4<RAG>(yr, 16 * g + 4 * q, h, vec, lo[t][g]);

@@ -13,6 +13,8 @@
 // NormalizingFlow.forward/inverse return (the reference's API keeps all L+1 tensors, core.py:20-24).
 // Without it every intermediate tensor is dropped: callers opt in through torch_mnf_amd.FusedAffineStack
 // and that number is reported separately from the headline metric.
+// With y == NULL (a density-only launch: the no-grad log_prob) no row is written at all; the rows end in
+// y_sqnorm / log_prob inside the kernel.
 #include <hip/hip_runtime.h>
 
 #include "mnf_ahf_shape.h"
@@ -96,7 +98,7 @@ ahf_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float* __re
       }
       __syncthreads();
     }
-    if (live) {
+    if (live && y != nullptr) {  // y == nullptr: a density-only launch, the caller reads ysq and log_det
       float* yr = y + rowc * dim + 4 * q;
 #pragma unroll
       for (int g = 0; g < G; ++g) *reinterpret_cast<f32x4*>(yr + 16 * g) = lo[g];
@@ -150,7 +152,9 @@ extern "C" {
 int mnf_affine_half_stack(const float* x, float* y, float* intermediates, float* log_det, float* y_sqnorm,
                           float* log_prob, double* log_prob_sum, int accumulate, const float* images, const void* split_images, const int* parity_host, int n_layers,
                           int64_t rows, int dim, int inverse, int n_hidden, const int* hidden, void* stream) {
-  if (!x || !y || x == y || !images || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || dim < 2 ||
+  // y == NULL: a density-only launch (the contract in mnf_hip.h)
+  if (!y && (intermediates || !log_det || !(y_sqnorm || log_prob || log_prob_sum))) return MNF_ERR_INVALID_ARG;
+  if (!x || x == y || !images || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || dim < 2 ||
       (dim & 1) || !mnf::hidden_ok(n_hidden, hidden) || ((log_prob || log_prob_sum) && !log_det))
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;

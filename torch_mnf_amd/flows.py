@@ -2567,10 +2567,15 @@ class _AffineRun:
         return list(out[:-1]), out[-1]
 
     def launch(self, x: Tensor, inverse: bool, log_det: Tensor, accumulate: bool, sqnorm: Tensor | None,
-               keep: bool, logprob: tuple | None = None, images: tuple | None = None) -> list[Tensor] | None:
+               keep: bool, logprob: tuple | None = None, images: tuple | None = None,
+               density_only: bool = False) -> list[Tensor] | None:
         """Runs the layers (model order reversed when ``inverse``).  Returns the output tensors in
         application order -- all of them when ``keep`` (views of one buffer: each intermediate is written
         once and never re-read), else just the last -- or None when the shape has no stack kernel.
+
+        ``density_only`` (without ``keep``; ``sqnorm`` given): the caller reads log_det and ``sqnorm`` / ``logprob``
+        alone, so the per-shape kernels get no output buffer at all (``y = NULL``) and the list is ``[None]``.  The
+        run-time-shaped kernel works in place in its output plane and keeps it.
 
         ``logprob`` = (log_prob (rows,), fp64 sum (1,) zeroed, or None): ask the kernel for the
         standard-normal log-prob epilogue too; ``self.logprob_fused`` says whether it did (only the split
@@ -2584,12 +2589,15 @@ class _AffineRun:
             return self._launch_rt(x, inverse, log_det, accumulate, sqnorm, keep, logprob, images[1])
         images, splits = images  # (``images``: from ready())
         x = _device_input(x, "input")
-        buf = torch.empty((n if keep else 1, x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
+        density_only = density_only and not keep and sqnorm is not None
+        buf = None if density_only else torch.empty((n if keep else 1, x.shape[0], x.shape[1]), dtype=torch.float32,
+                                                    device=x.device)
         par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
 
         def go(lp, total, sq):
             return _lib.load().mnf_affine_half_stack(
-                x.data_ptr(), buf[-1].data_ptr(), buf.data_ptr() if keep and n > 1 else None, log_det.data_ptr(),
+                x.data_ptr(), None if buf is None else buf[-1].data_ptr(),
+                buf.data_ptr() if keep and n > 1 else None, log_det.data_ptr(),
                 _ptr(sq), _ptr(lp), _ptr(total), int(accumulate), images.data_ptr(), _ptr(splits), par, n, x.shape[0],
                 f0.dim, int(inverse), len(f0.h_sizes), f0._hid, _stream())
 
@@ -2603,7 +2611,7 @@ class _AffineRun:
             self._unsupported = True
             return None
         _lib.check("mnf_affine_half_stack", rc)
-        return list(buf.unbind(0))
+        return [None] if buf is None else list(buf.unbind(0))
 
     def _launch_rt(self, x, inverse, log_det, accumulate, sqnorm, keep, logprob, flat, as_buffer: bool = False):
         """``launch`` on the run-time-shaped kernel: same buffers, the parameters instead of operand images.  Every
@@ -2890,7 +2898,9 @@ class NormalizingFlow(nn.Module):
               last_only: bool = False, lp_tail: bool = False):
         """prologue (forward only, first flow an RNVP): see RNVP._run; the returned list then starts with eps.
         last_only: the caller reads only the last tensor of the returned list (log_prob): pairs of layers with a fused
-        training kernel go out as one autograd node and their intermediate is not materialised.
+        training kernel go out as one autograd node and their intermediate is not materialised, and a no-grad run
+        writes none of its intermediates.  When the run closes the pass and |z|^2 or log p comes out of its kernel
+        (want_sqnorm / want_logprob) z is not written either: the list then ends with None.
         lp_tail (with last_only, standard-normal base): when such a pair CLOSES the pass its node produces log p itself
         (``self._lp_node``; the list then ends with None and log_det is not extended).
         want_logprob = (lp, total-or-None): when the LAST launch is an affine run whose kernel can add the
@@ -2956,13 +2966,14 @@ class NormalizingFlow(nn.Module):
                         log_det = ld_run if (fresh and i == 0) else log_det + ld_run
                 elif isinstance(run, _AffineRun):
                     sq = torch.empty(x.size(0), device=x.device) if (want_sqnorm and last) else None
-                    outs = run.launch(x, inverse, log_det, not (fresh and i == 0), sq, keep=True,
-                                      logprob=want_logprob if last else None, images=run_images)
+                    outs = run.launch(x, inverse, log_det, not (fresh and i == 0), sq, keep=not last_only,
+                                      logprob=want_logprob if last else None, images=run_images,
+                                      density_only=last_only and last)
                     if outs is not None and last and want_logprob is not None and run.logprob_fused:
                         self._logprob_done, sq = True, None
                 else:
                     sq = None
-                    outs = run.launch(x, inverse, log_det, True, keep=True,
+                    outs = run.launch(x, inverse, log_det, True, keep=not last_only,
                                       logprob=want_logprob if (last and not _dispatch.NO_FUSED_LOGPROB) else None)
                     if outs is not None and last and want_logprob is not None and not _dispatch.NO_FUSED_LOGPROB:
                         self._logprob_done = True
@@ -3079,7 +3090,7 @@ class NormalizingFlowModel(NormalizingFlow):
         self.base = base
 
     def base_log_prob(self, x: Tensor) -> Tensor:
-        zs, _ = self.inverse(x)
+        zs, _ = self._pass(x, True, last_only=True)  # z and only z: no intermediate is written
         return self.base.log_prob(zs[-1])
 
     def sample(self, *num_samples: int) -> Tensor:
@@ -3147,19 +3158,20 @@ class NormalizingFlowModel(NormalizingFlow):
         if self._lp_node is not None:  # the closing [Glow, ActNorm] pair's node produced log p (training)
             lp_node, self._lp_node = self._lp_node, None
             return (lp_node, lp_node.detach().double().sum().reshape(1)) if return_sum else lp_node
-        z = zs[-1]
+        z = zs[-1]  # None: the closing affine run wrote no rows (its kernel produced log p or |z|^2 instead)
         if self._logprob_done:  # the last coupling launch already produced log p and its sum
             return (lp, total) if return_sum else lp
-        if std and not (torch.is_grad_enabled() and (z.requires_grad or log_det.requires_grad)):
+        if std and (z is None or not (torch.is_grad_enabled() and (z.requires_grad or log_det.requires_grad))):
             if lp is None:
                 lp = torch.empty_like(log_det)
-                total = torch.zeros(1, dtype=torch.float64, device=z.device) if return_sum else None
-            if z.shape[0] == 0:
+                total = torch.zeros(1, dtype=torch.float64, device=log_det.device) if return_sum else None
+            rows, dim = (log_det.shape[0], x.shape[1]) if z is None else z.shape
+            if rows == 0:
                 return (lp, total) if return_sum else lp
             if self._last_sqnorm is not None:  # |z|^2 came out of the last coupling kernel
                 _lib.check("mnf_gauss_logprob_sq", _lib.load().mnf_gauss_logprob_sq(
                     self._last_sqnorm.data_ptr(), log_det.data_ptr(), lp.data_ptr(), _ptr(total),
-                    z.shape[0], z.shape[1], _stream()))
+                    rows, dim, _stream()))
             else:
                 _lib.check("mnf_gauss_logprob", _lib.load().mnf_gauss_logprob(
                     z.data_ptr(), log_det.data_ptr(), lp.data_ptr(), _ptr(total), z.shape[0], z.shape[1],
