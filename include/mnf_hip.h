@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 28
+#define MNF_ABI_VERSION 29
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -691,6 +691,36 @@ int mnf_mnf_conv_fwd_supported(int n_in, int n_out, int kernel_size, int height,
 int mnf_mnf_conv_fwd(const float* x, const float* Wz, const float* W_var, const float* b_mean, const float* b_var,
                      const float* eps, float* out, float* var_out, int64_t batch, int n_in, int height, int width,
                      int n_out, int kernel_size, void* stream);
+
+/* ------------------------------------------------ the gradients of that launch: MNFConv2d backward on the matrix cores
+ * The two gradient convolutions of the node above (what autograd derives from mnf_conv.py:73-88), on the exact-fp32 matrix
+ * instruction, for the same layout: grad_out is the output's cotangent and grad_var = mnf_mnf_noise_bwd's result, both
+ * (batch, n_out, height - k + 1, width - k + 1).  Every sum runs in a fixed order: no atomics, a call repeats bit for bit,
+ * no host synchronisation (capturable in a hipGraph).
+ *   _bwd_weight   one pass over x for all three (kernel family "mnf_conv_bwd_weight"), outputs OVERWRITTEN:
+ *                   grad_Wz[co, j]    = sum_p grad_out[p, co] x[patch(p, j)]       j = (ci, ky, kx), p: every output pixel
+ *                   grad_W_var[co, j] = sum_p grad_var[p, co] x[patch(p, j)]^2
+ *                   grad_b_var[co]    = sum_p grad_var[p, co]
+ *                 The pixels are cut into slices whose partial sums go to `workspace` (plain stores) and are added in slice
+ *                 order; the slice count follows from the shape alone.  Outputs that lie one behind the other in memory
+ *                 (grad_Wz | grad_W_var | grad_b_var) are zeroed and reduced by one launch each instead of three.
+ *   _bwd_weight_workspace  floats `workspace` must hold (at most 32 MB worth); 0 where the entry would refuse the shape
+ *   _bwd_input    grad_x[n, ci, y, x] = sum_{co,ky,kx} grad_out[n, co, y - ky, x - kx] Wz[co, ci, ky, kx]
+ *                                     + 2 x[n, ci, y, x] sum_{co,ky,kx} grad_var[n, co, y - ky, x - kx] W_var[co, ci, ky, kx]
+ *                 (terms outside the output image absent), written; no workspace (family "mnf_conv_bwd_input")
+ *   _supported    _bwd_weight: mnf_mnf_conv_fwd_supported's envelope; _bwd_input: that and n_in <= 64, n_out k^2 <= 4096
+ *   the entries   MNF_ERR_INVALID_ARG on a null pointer, a non-positive size or workspace_floats below the query's answer;
+ *                 MNF_ERR_UNSUPPORTED outside _supported or from 2^31 - 65536 pixels on (output pixels for _bwd_weight,
+ *                 batch * height * width for _bwd_input).  Argument checks come before any GPU call. */
+int mnf_mnf_conv_bwd_weight_supported(int n_in, int n_out, int kernel_size, int height, int width);
+int mnf_mnf_conv_bwd_input_supported(int n_in, int n_out, int kernel_size, int height, int width);
+int64_t mnf_mnf_conv_bwd_weight_workspace(int64_t batch, int n_in, int n_out, int kernel_size, int height, int width);
+int mnf_mnf_conv_bwd_weight(const float* x, const float* grad_out, const float* grad_var, float* grad_Wz, float* grad_W_var,
+                            float* grad_b_var, float* workspace, int64_t workspace_floats, int64_t batch, int n_in,
+                            int height, int width, int n_out, int kernel_size, void* stream);
+int mnf_mnf_conv_bwd_input(const float* x, const float* grad_out, const float* grad_var, const float* Wz,
+                           const float* W_var, float* grad_x, int64_t batch, int n_in, int height, int width, int n_out,
+                           int kernel_size, void* stream);
 
 /* ------------------------------------------------------------------ gradients (autograd)
  * What torch.autograd.Function.backward needs so the modules train like the reference's

@@ -65,6 +65,8 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
 | MNFConv2d.forward        | MNF_CONV_FUSED (opt-in: False) | n_out <= 64, n_in k^2 <= 4096          | mnf_conv_fwd (one launch behind the operands) |
 |                          | else            | anything                                          | MIOpen convolutions between the library's operand and noise launches |
+| MNFConv2d.forward bwd    | MNF_CONV_BWD_FUSED (opt-in: False), on mnf_conv_fwd's node | weights: mnf_conv_fwd's shapes; input: those with n_in <= 64, n_out k^2 <= 4096 | mnf_conv_bwd_weight / mnf_conv_bwd_input |
+|                          | else            | anything                                          | mnf_mnf_noise_bwd, then aten's convolution_backward twice |
 
 The *_rt rows' shape limits are the library's queries (mnf_*_rt_supported, include/mnf_hip.h), which tier() asks.  (*) The
 NSF_CL gradient kernel's weight slot must stay within 40 LDS blocks and fit 160 KB with the rest: with n_h units per
@@ -255,6 +257,24 @@ AHF_BWD_RT_WIDE_MIN_ROWS = None
 # (level).  The smallest batch from which the route wins every cell by more than that spread is 1,024: the threshold a
 # follow-up would give the switch.
 MNF_CONV_FUSED = False
+
+# The gradients of that node on the library's own kernels (csrc/mnf_mnf_conv_bwd.hip, families mnf_conv_bwd_weight and
+# mnf_conv_bwd_input; layers._MnfConvFwdFn._backward_fused): OPT-IN, read at every backward call, and only
+# inside _MnfConvFwdFn.backward, that is with MNF_CONV_FUSED on.  The three weight-side gradients are one matrix-core pass
+# over x (the x * x tensor disappears) plus a zeroing and a fixed-order reduction launch; grad_x is one launch with the
+# 2 x epilogue inside.  Each part asks its own shape query and otherwise runs what it runs with the switch off.  No atomics:
+# a backward repeats bit for bit.
+# Measured (tools/time_mnf_conv_bwd.py, profiles/r27/mnf_conv_bwd_ab.txt: forward + backward through the layer, fused forward
+# both times, this route against the parent route timed twice, median of 15 alternating calls, microseconds per call, at
+# batch 128 / 1,024 / 8,192):
+#   MNFConv2d(1, 20, 5) 28x28   905 against 962 / 962 | 553 / 748 / 745 | 2,427 / 2,826 / 2,820        (weight part only)
+#   MNFConv2d(20, 50, 5) 12x12  629 / 672 / 672       | 1,260 / 957 / 959 | 7,405 / 4,872 / 4,800      (both parts)
+#   MNFLeNet forward + backward 128 rows 2,259 / 2,462 / 2,480 | 4,096 rows 6,962 / 5,918 / 5,868
+# Five of eight cells are won by more than the parent's spread (the first convolution everywhere, everything at batch 128);
+# the second convolution from batch 1,024 on and the LeNet step at 4,096 rows are LOST: both new kernels are 1.4-2.1 x slower
+# there than the aten launches they replace (profiles/r27/README.md, kernel by kernel).  No batch wins every cell, so the
+# switch has no threshold to offer yet.
+MNF_CONV_BWD_FUSED = False
 
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 28  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 29  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -233,6 +233,11 @@ SIGNATURES = {
     "mnf_mnf_noise_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mnf_mnf_conv_fwd_supported": (c_int, [c_int] * 5),
     "mnf_mnf_conv_fwd": (c_int, [c_void_p] * 8 + [c_int64] + [c_int] * 5 + [c_void_p]),
+    "mnf_mnf_conv_bwd_weight_supported": (c_int, [c_int] * 5),
+    "mnf_mnf_conv_bwd_input_supported": (c_int, [c_int] * 5),
+    "mnf_mnf_conv_bwd_weight_workspace": (c_int64, [c_int64] + [c_int] * 5),
+    "mnf_mnf_conv_bwd_weight": (c_int, [c_void_p] * 7 + [c_int64, c_int64] + [c_int] * 5 + [c_void_p]),
+    "mnf_mnf_conv_bwd_input": (c_int, [c_void_p] * 6 + [c_int64] + [c_int] * 5 + [c_void_p]),
     "mnf_glow_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "mnf_glow_weight_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -231,8 +231,9 @@ class _NoiseFn(torch.autograd.Function):
 class _MnfConvFwdFn(torch.autograd.Function):
     """MNFConv2d.forward behind its operands (mnf_conv.py:73-88) as ONE launch, ``mnf_mnf_conv_fwd``: both convolutions on
     the exact-fp32 matrix instruction and the noise epilogue (_dispatch.MNF_CONV_FUSED).  ``eps`` None: drawn here, before
-    the launch.  Backward has no kernel of its own: the noise gradient launch, then aten's convolution_backward once per
-    convolution -- what the MIOpen route's autograd graph runs too."""
+    the launch.  Backward is the noise gradient launch, then aten's convolution_backward once per convolution -- what the
+    MIOpen route's autograd graph runs too -- or, under _dispatch.MNF_CONV_BWD_FUSED, the library's two gradient kernels
+    (``_backward_fused``)."""
 
     @staticmethod
     def forward(ctx, x, Wz, W_var, b_var, b_mean, eps):
@@ -265,6 +266,8 @@ class _MnfConvFwdFn(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
+        if _dispatch.MNF_CONV_BWD_FUSED:  # opt-in: the gradient convolutions on the library's own kernels
+            return _MnfConvFwdFn._backward_fused(ctx, g)
         xc, wz, wv, var, e = ctx.saved_tensors
         need_x, need_wz, need_wv, need_bv = ctx.needs_input_grad[:4]
         gc = g.contiguous()
@@ -281,6 +284,65 @@ class _MnfConvFwdFn(torch.autograd.Function):
             if need_x:
                 gx = gx + 2 * xc * gx2  # d (x * x) = 2 x
         return gx, g_wz, g_wv, g_bv, None, None
+
+    @staticmethod
+    def _backward_fused(ctx, g):
+        """backward under _dispatch.MNF_CONV_BWD_FUSED: the three weight-side gradients as one matrix-core pass over x
+        (``mnf_mnf_conv_bwd_weight``: no x * x tensor) and grad_x as one launch (``mnf_mnf_conv_bwd_input``: both
+        transposed convolutions and the 2 x epilogue), each where its own shape query has the call; a part that is not
+        supported runs aten's convolution_backward exactly as above."""
+        xc, wz, wv, var, e = ctx.saved_tensors
+        need_x, need_wz, need_wv, need_bv = ctx.needs_input_grad[:4]
+        need_w = need_wz or need_wv or need_bv
+        lib, stream = _lib.load(), _stream()
+        batch, n_in, height, width = xc.shape
+        n_out, k = wz.shape[0], wz.shape[-1]
+        shape = (n_in, n_out, k, height, width)
+        n_ws = int(lib.mnf_mnf_conv_bwd_weight_workspace(batch, *shape[:3], height, width)) if need_w else 0
+        fused_w = n_ws > 0 and bool(lib.mnf_mnf_conv_bwd_weight_supported(*shape))
+        fused_x = need_x and bool(lib.mnf_mnf_conv_bwd_input_supported(*shape)) and batch * height * width < 2 ** 31 - 65536
+        gc = g.contiguous()
+        gx = g_wz = g_wv = g_bv = gv = None
+        if need_x or need_w:
+            gv = torch.empty_like(var)
+            _lib.check("mnf_mnf_noise_bwd", lib.mnf_mnf_noise_bwd(var.data_ptr(), e.data_ptr(), gc.data_ptr(),
+                                                                 gv.data_ptr(), var.numel(), stream))
+        if fused_w:
+            key = (xc.device, stream)
+            work = _MNF_CONV_BWD_WORK.get(key)
+            if work is None or work.numel() < n_ws:
+                work = torch.empty(n_ws, dtype=torch.float32, device=xc.device)
+                _MNF_CONV_BWD_WORK[key] = work
+            n = wz.numel()
+            buf = torch.empty(2 * n + n_out, dtype=torch.float32, device=xc.device)  # one zeroing, one reduction
+            _lib.check("mnf_mnf_conv_bwd_weight", lib.mnf_mnf_conv_bwd_weight(
+                xc.data_ptr(), gc.data_ptr(), gv.data_ptr(), buf.data_ptr(), buf.data_ptr() + 4 * n,
+                buf.data_ptr() + 8 * n, work.data_ptr(), work.numel(), batch, n_in, height, width, n_out, k, stream))
+            g_wz = buf[:n].view_as(wz) if need_wz else None
+            g_wv = buf[n:2 * n].view_as(wv) if need_wv else None
+            g_bv = buf[2 * n:] if need_bv else None
+            need_wz = need_wv = need_bv = False
+        if fused_x:
+            gx = torch.empty_like(xc)
+            _lib.check("mnf_mnf_conv_bwd_input", lib.mnf_mnf_conv_bwd_input(
+                xc.data_ptr(), gc.data_ptr(), gv.data_ptr(), wz.data_ptr(), wv.data_ptr(), gx.data_ptr(), batch, n_in,
+                height, width, n_out, k, stream))
+            need_x = False
+        # what is left, as with the switch off
+        conv_bwd = torch.ops.aten.convolution_backward
+        geometry = ([n_out], [1, 1], [0, 0], [1, 1], False, [0, 0], 1)
+        if need_x or need_wz:
+            r = conv_bwd(gc, xc, wz, *geometry, [need_x, need_wz, False])
+            gx, g_wz = r[0], (r[1] if need_wz else g_wz)
+        if need_x or need_wv or need_bv:
+            r = conv_bwd(gv, xc * xc, wv, *geometry, [need_x, need_wv, need_bv])
+            g_wv, g_bv = (r[1] if need_wv else g_wv), (r[2] if need_bv else g_bv)
+            if need_x:
+                gx = gx + 2 * xc * r[0]
+        return gx, g_wz, g_wv, g_bv, None, None
+
+
+_MNF_CONV_BWD_WORK: dict = {}  # (device, stream) -> workspace of mnf_mnf_conv_bwd_weight (its launches follow one another on a stream)
 
 
 class _MnfKlFn(torch.autograd.Function):
@@ -643,7 +705,8 @@ class MNFConv2d(nn.Module):
     and noise launches.  With ``_dispatch.MNF_CONV_FUSED = True`` (opt-in) and n_out <= 64, n_in * kernel_size**2 <= 4096,
     everything behind the operand launch -- both convolutions and the noise epilogue -- is ONE launch of the library's
     own (``mnf_mnf_conv_fwd``, exact-fp32 matrix instruction; its gradients: the noise gradient launch and aten's
-    convolution_backward).  Noise can be injected for reproducible runs:
+    convolution_backward, or with ``_dispatch.MNF_CONV_BWD_FUSED = True`` as well the library's ``mnf_mnf_conv_bwd_weight``
+    and ``mnf_mnf_conv_bwd_input``).  Noise can be injected for reproducible runs:
     ``eps_z`` (n_out,), ``masks`` (one (1, n_out) float mask per flow layer), ``eps`` (shape of the output)."""
 
     def __init__(self, n_in: int, n_out: int, kernel_size: int, n_flows_q: int = 2, n_flows_r: int = 2,
