@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 29
+#define MNF_ABI_VERSION 30
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -153,6 +153,27 @@ int mnf_affine_half_stack(const float* x, float* y, float* intermediates, float*
                           const float* images, const void* split_images, const int* parity_host, int n_layers,
                           int64_t rows, int dim, int inverse,
                           int n_hidden, const int* hidden_host, void* stream);
+/* Seeded sampling as ONE launch of the split stack kernel (kernel family "ahf_split_stack_sample"): replaces
+ * `z = base.sample(n); xs, _ = flow.forward(z); xs[-1]` of NormalizingFlowModel.sample (flows/core.py:51-55) for a model
+ * that is one run of equal AffineHalfFlow layers under a standard-normal base.  The rows are not read but generated in the
+ * kernel's registers, z[r][c] = the counter-based N(0, 1) of (seed, row0 + r, c) that mnf_normal_rows(seed, row0, ., rows,
+ * dim) writes (bit for bit); layers 0..L-1 are applied (the forward direction) and y (rows, dim) is the only tensor the
+ * launch writes: 4*dim bytes per row of HBM traffic, no noise tensor, no intermediates, no log_det.  y equals what
+ * mnf_affine_half_stack(forward) returns on the materialised noise, bit for bit, and is a pure function of (seed, row,
+ * parameters): calls over row ranges of one seed are pieces of one sample.  images / split_images / parity_host as
+ * mnf_affine_half_stack (both images required).
+ * MNF_ERR_INVALID_ARG before any launch: NULL y / images / split_images / parity_host, n_layers outside 1 .. 32, rows < 0,
+ * row0 < 0, odd dim.  rows == 0: MNF_OK, nothing is touched.  MNF_ERR_UNSUPPORTED where
+ * mnf_affine_half_stack_sample_supported() is 0 or y is not 16-byte aligned (caller: mnf_normal_rows, then the ordinary
+ * forward pass).  Never allocates or synchronises; capturable. */
+int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const float* images, const void* split_images,
+                                 const int* parity_host, int n_layers, int64_t rows, int dim, int n_hidden,
+                                 const int* hidden_host, void* stream);
+/* Host-side query of the shape alone (no device needed): 1 for the full-tile shapes of the split stack kernel -- dim / 2
+ * in {16, 32, 64, 128}, three hidden layers run at 16 / 24 / 32 units (32: up to dim 128, and at dim <= 64 one layer
+ * only, as mnf_affine_half_stack), n_layers 1 .. 32.  0 for a half narrower than its tile (the ragged variant has no
+ * noise source) and for every shape without a split stack kernel. */
+int mnf_affine_half_stack_sample_supported(int dim, int n_hidden, const int* hidden_host, int n_layers);
 /* n_layers (1 .. 32) AffineHalfFlow layers of one shape WITHOUT a per-shape kernel in ONE launch of the run-time-shaped
  * kernel (mnf_ahf_rt.hip; kernel family "ahf_stack_rt", "ahf_rt" for one layer).  flats: the layers' plain parameter
  * vectors back to back, layer 0 first, mnf_affine_half_flat_floats() each -- no operand image, no index table.  Layers
@@ -374,6 +395,12 @@ int mnf_sample_z0_seeded(const float* q0_mean, const float* q0_log_var, uint64_t
 int mnf_sample_z0_seeded_bwd(const float* grad_z0, uint64_t seed, const float* q0_log_var, float* grad_mean,
                              float* grad_log_var, int64_t rows, int dim, void* stream);
 int mnf_sample_z0_noise(uint64_t seed, float* eps, int64_t rows, int dim, void* stream);
+/* mnf_sample_z0_noise with a row offset: out[r][c] = the same counter-based N(0, 1) of (seed, row0 + r, c), (rows, dim),
+ * any dim >= 1 -- replaces `torch.randn(n, dim)` of a base distribution's sample() (flows/core.py:52) where the draw must
+ * be a function of a seed alone: row ranges of one seed are pieces of one sample, whatever the chunking or the rank that
+ * draws them.  mnf_sample_z0_noise is row0 == 0; mnf_affine_half_stack_sample generates exactly these numbers in place.
+ * MNF_ERR_INVALID_ARG for NULL out, rows < 0, row0 < 0, dim < 1. */
+int mnf_normal_rows(uint64_t seed, int64_t row0, float* out, int64_t rows, int dim, void* stream);
 /* mnf_sample_z0_bwd (eps != NULL) / mnf_sample_z0_seeded_bwd (eps == NULL) with the sums over the rows added in a fixed
  * order: every row block leaves its sums in `workspace` (mnf_sample_z0_bwd_workspace(rows, dim) floats) and a second
  * launch adds the blocks up in order -- no float atomics, the result repeats bit for bit (MNF_DETERMINISTIC=1). */

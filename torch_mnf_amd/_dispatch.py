@@ -63,6 +63,8 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | NSF_AR.forward fwd       | >= NSF_AR_SEQ_RT_MIN_ROWS (opt-in: None) | 2 <= d <= 128, K = 5 or 8, 1..4 hidden layers of widths 4..16 | nsf_ar_seq_rt |
 |                          | else            | anything (element by element)                     | nsf_ar_generic (VALU)          |
 | NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
+| NormalizingFlowModel.sample(seed=) | any    | the model is ONE run of AffineHalfFlow layers on ahf_split_stack's full-tile shapes (d / 2 in 16/32/64/128) | ahf_split_stack_sample (one launch, noise in-kernel) |
+|                          | else            | anything (StandardNormal base)                    | mnf_normal_rows' noise launch, then forward's rows above without intermediates |
 | MNFConv2d.forward        | MNF_CONV_FUSED (opt-in: False) | n_out <= 64, n_in k^2 <= 4096          | mnf_conv_fwd (one launch behind the operands) |
 |                          | else            | anything                                          | MIOpen convolutions between the library's operand and noise launches |
 | MNFConv2d.forward bwd    | MNF_CONV_BWD_FUSED (opt-in: False), on mnf_conv_fwd's node | weights: mnf_conv_fwd's shapes; input: those with n_in <= 64, n_out k^2 <= 4096 | mnf_conv_bwd_weight / mnf_conv_bwd_input |
@@ -87,6 +89,12 @@ unless the owner's opt-in switch ``fuse_rt_training`` (NormalizingFlow / FusedAf
 is then ONE autograd node (flows._AffineRunFn), ahf_stack_rt forward with every output kept and ONE ahf_bwd_stack_rt
 launch backward (mnf_affine_half_bwd_rt_stack; its fixed-order form under MNF_DETERMINISTIC=1), the last layer's
 cotangents formed in the kernel when the run is a whole log_prob pass.  tier() is unchanged by the switch.
+
+The sample(seed=) rows are NormalizingFlowModel.sample with a seed (no row-count threshold; without a seed it is torch.randn
+and forward, as ever): rows first_row .. first_row + n - 1 of forward(z), z[r, c] = z0_normal(seed, r, c).  The one-launch
+row needs the run on the split per-shape route with its images ready (no force_generic, no fp32 request, run fusion on, no
+per-launch event marks) and mnf_affine_half_stack_sample_supported(); both rows compute the same sample, and a model takes
+the same row at every call of one shape.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and

@@ -272,7 +272,13 @@ __device__ __forceinline__ void half_store4(float* p, int col, int h, bool vec, 
   }
 }
 
-template <int H, int HID, bool INV, bool RAG>
+// SAMPLE (forward, full tiles: launch_split_stack_sample): the rows are not read but generated, z[r][c] =
+// z0_normal(seed, row0 + r, c) (mnf_device.h; mnf_normal_rows writes the same numbers), and y is the only output.  Such a
+// launch has no input rows, no log_det to accumulate into and full tiles, so seed travels in `x` and row0 in `accumulate`
+// (low word) and `h_ragged` (high word); mid, log_det, ysq, log_prob and log_prob_sum are NULL.  A compile-time switch,
+// not a run-time row source in the forward instantiations: as a run-time branch at the top of the group loop it cost the
+// forward kernels 2 .. 10 VGPRs and spills in the two hidden-32 ones that sit at 256 (profiles/r28/kernel_resources.txt).
+template <int H, int HID, bool INV, bool RAG, bool SAMPLE = false>
 __global__ void __launch_bounds__(stack_waves<H>() * 64, stack_waves_per_simd<H>())
 ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ mid,
                        float* __restrict__ log_det, float* __restrict__ ysq, const uint32_t* __restrict__ simages,
@@ -297,7 +303,6 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
   const int j = lane & 15, q = lane >> 4;
   const uint4* img4 = reinterpret_cast<const uint4*>(simages);
   auto layer_at = [&](int li) { return INV ? n_layers - 1 - li : li; };  // application order
-
   double lp_acc = 0.0;
   const int n_groups = (int)((rows + GROUP_ROWS - 1) / GROUP_ROWS);
   for (int grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
@@ -309,11 +314,34 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
       row[t] = (int64_t)grp * GROUP_ROWS + (wave * NTL + t) * 16 + j;
       live[t] = row[t] < rows;
       rowc[t] = live[t] ? row[t] : rows - 1;  // rows past the end: clamped loads, masked stores
-      const float* xr = x + rowc[t] * dim;
+      if constexpr (SAMPLE) {
+        // a lane's four columns are two pairs of the stream (H % 16 == 0: both halves start on an even column); rows
+        // past the end generate their would-be numbers, nothing is read for them
+        const uint64_t seed = reinterpret_cast<uint64_t>(x);
+        const int64_t row0 = (int64_t)((uint64_t)(uint32_t)accumulate | ((uint64_t)(uint32_t)h_ragged << 32));
+        // (q and the row through an empty asm: the pairs' column terms and the group-invariant part of the row hash
+        //  would otherwise be hoisted out of the group loop and sit in registers through every layer)
+        int qs = q;
+        int64_t rs = row[t];
+        asm volatile("" : "+v"(qs), "+v"(rs));
+        const uint32_t rh = z0_row_hash(seed, row0 + rs);
+        auto quad = [&](int pair) {
+          float n0, n1, n2, n3;
+          z0_normal_pair(rh, (uint32_t)seed, pair, n0, n1);
+          z0_normal_pair(rh, (uint32_t)seed, pair + 1, n2, n3);
+          return f32x4{n0, n1, n2, n3};
+        };
 #pragma unroll
-      for (int g = 0; g < G; ++g) lo[t][g] = half_load4<RAG>(xr, 16 * g + 4 * q, h, vec);
+        for (int g = 0; g < G; ++g) lo[t][g] = quad(8 * g + 2 * qs);
 #pragma unroll
-      for (int g = 0; g < G; ++g) hi[t][g] = half_load4<RAG>(xr + h, 16 * g + 4 * q, h, vec);
+        for (int g = 0; g < G; ++g) hi[t][g] = quad(H / 2 + 8 * g + 2 * qs);
+      } else {
+        const float* xr = x + rowc[t] * dim;
+#pragma unroll
+        for (int g = 0; g < G; ++g) lo[t][g] = half_load4<RAG>(xr, 16 * g + 4 * q, h, vec);
+#pragma unroll
+        for (int g = 0; g < G; ++g) hi[t][g] = half_load4<RAG>(xr + h, 16 * g + 4 * q, h, vec);
+      }
     }
     __syncthreads();  // the previous group's last layer is fully consumed
     image_to_lds_async<IMG4, kStackWaves>(img4 + (int64_t)layer_at(0) * IMG4, lds_buf(0), lane, wave);
@@ -641,9 +669,82 @@ int ahf_split_stack_launch(const float* x, float* y, float* mid, float* log_det,
   return MNF_ERR_UNSUPPORTED;
 }
 
+// The shapes with a sample launch: the stack kernel's full-tile forward instantiations (a narrow half runs on the ragged
+// variant, which has no noise source), under the stack launcher's own rule for hidden width 32.
+static bool stack_sample_shape(int dim, int hid, int n_layers) {
+  if (dim < 2 || (dim & 1) || n_layers < 1 || n_layers > 32) return false;
+  const int h = dim / 2;
+  if (h != ahf_padded_half(h)) return false;
+  if (hid == 32 && h <= 32 && n_layers > 1) return false;
+#define X(HH, HD) \
+  if (h == HH && hid == HD) return true;
+  MNF_AHF_SPLIT_STACK_SHAPES(X)
+#undef X
+  return false;
+}
+
+// the SAMPLE instantiation on launch_split_stack's grid: seed rides in x, row0 in accumulate | h << 32 (see the kernel)
+template <int H, int HID>
+static int launch_split_stack_sample(uint64_t seed, int64_t row0, float* y, const uint32_t* simages, const float* images,
+                                     uint32_t parity_bits, int n_layers, int64_t rows, hipStream_t stream) {
+  constexpr int kStackWaves = stack_waves<H>(), kStackTiles = stack_tiles<H>();
+  constexpr size_t image_bytes = 2 * SplitShape<H, HID>::IMAGE_WORDS * sizeof(uint32_t);
+  constexpr size_t lds_bytes = image_bytes <= 64 * 1024 ? 0 : image_bytes;
+  static DeviceMemo memo;
+  const int resident = memo.get([](int dev) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_split_stack_kernel<H, HID, false, false, true>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
+      return -1;
+    int per_cu = 4 * stack_waves_per_simd<H>() / kStackWaves;  // (as launch_split_stack)
+    while (per_cu > 1 && per_cu * image_bytes > 160 * 1024) --per_cu;
+    return per_cu * device_cus(dev);
+  });
+  if (resident <= 0) return MNF_ERR_UNSUPPORTED;
+  constexpr int GROUP_ROWS = 16 * kStackTiles * kStackWaves;
+  const int64_t n_groups = (rows + GROUP_ROWS - 1) / GROUP_ROWS;
+  const dim3 grid((unsigned)(n_groups < resident ? n_groups : resident)), block(kStackWaves * 64);
+  tag_kernel("ahf_split_stack_sample");
+  hipLaunchKernelGGL((ahf_split_stack_kernel<H, HID, false, false, true>), grid, block, lds_bytes, stream,
+                     reinterpret_cast<const float*>(seed), y, (float*)nullptr, (float*)nullptr, (float*)nullptr, simages,
+                     images, parity_bits, n_layers, rows, (int)(uint32_t)row0, (float*)nullptr, (double*)nullptr,
+                     (int)(uint32_t)((uint64_t)row0 >> 32), 1);
+  return check_launch();
+}
+
+static int ahf_split_stack_sample_launch(uint64_t seed, int64_t row0, float* y, const void* split_images,
+                                         const float* images, uint32_t parity_bits, int n_layers, int64_t rows, int dim,
+                                         int hid, hipStream_t stream) {
+  if (!stack_sample_shape(dim, hid, n_layers) || !aligned16(y, split_images, images, nullptr)) return MNF_ERR_UNSUPPORTED;
+  const uint32_t* simages = static_cast<const uint32_t*>(split_images);
+#define X(HH, HD)                  \
+  if (dim == 2 * HH && hid == HD)  \
+    return launch_split_stack_sample<HH, HD>(seed, row0, y, simages, images, parity_bits, n_layers, rows, stream);
+  MNF_AHF_SPLIT_STACK_SHAPES(X)
+#undef X
+  return MNF_ERR_UNSUPPORTED;
+}
+
 }  // namespace mnf
 
 extern "C" {
+
+int mnf_affine_half_stack_sample_supported(int dim, int n_hidden, const int* hidden_host, int n_layers) {
+  return mnf::hidden_ok(n_hidden, hidden_host) &&
+         mnf::stack_sample_shape(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers);
+}
+
+int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const float* images, const void* split_images,
+                                 const int* parity_host, int n_layers, int64_t rows, int dim, int n_hidden,
+                                 const int* hidden_host, void* stream) {
+  if (!y || !images || !split_images || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || row0 < 0 ||
+      dim < 2 || (dim & 1) || !mnf::hidden_ok(n_hidden, hidden_host))
+    return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  uint32_t bits = 0;
+  for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
+  return mnf::ahf_split_stack_sample_launch(seed, row0, y, split_images, images, bits, n_layers, rows, dim,
+                                            mnf::ahf_padded_hidden(n_hidden, hidden_host), (hipStream_t)stream);
+}
 
 int mnf_affine_half_split_layout(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                  int64_t* n_split_words, int64_t* n_plain_words) {

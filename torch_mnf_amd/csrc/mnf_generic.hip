@@ -633,9 +633,10 @@ __global__ void __launch_bounds__(256) sample_z0_seeded_kernel(const float* __re
     }
   }
 }
-__global__ void sample_z0_noise_kernel(uint64_t seed, float* __restrict__ eps, int64_t rows, int dim) {
+// (row0: the stream's row of eps[0] -- mnf_normal_rows; mnf_sample_z0_noise is row0 = 0)
+__global__ void sample_z0_noise_kernel(uint64_t seed, float* __restrict__ eps, int64_t rows, int dim, int64_t row0) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < rows * dim) eps[i] = z0_normal(seed, i / dim, (int)(i % dim));
+  if (i < rows * dim) eps[i] = z0_normal(seed, row0 + i / dim, (int)(i % dim));
 }
 
 // gradients of the prologue: d mean[j] = sum_r g[r][j];  d log_var[j] = sum_r g[r][j] eps[r][j] * 0.5 sqrt(exp(log_var[j])).
@@ -1494,12 +1495,16 @@ int mnf_sample_z0_seeded(const float* q0_mean, const float* q0_log_var, uint64_t
   return check_launch();
 }
 
-int mnf_sample_z0_noise(uint64_t seed, float* eps, int64_t rows, int dim, void* stream) {
-  if (!eps || rows < 0 || dim < 1) return MNF_ERR_INVALID_ARG;
+int mnf_normal_rows(uint64_t seed, int64_t row0, float* out, int64_t rows, int dim, void* stream) {
+  if (!out || rows < 0 || row0 < 0 || dim < 1) return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
   hipLaunchKernelGGL(sample_z0_noise_kernel, dim3((unsigned)((rows * dim + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
-                     eps, rows, dim);
+                     out, rows, dim, row0);
   return check_launch();
+}
+
+int mnf_sample_z0_noise(uint64_t seed, float* eps, int64_t rows, int dim, void* stream) {
+  return mnf_normal_rows(seed, 0, eps, rows, dim, stream);
 }
 
 int mnf_sample_z0_seeded_bwd(const float* grad_z0, uint64_t seed, const float* q0_log_var, float* grad_mean,

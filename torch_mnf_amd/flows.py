@@ -2345,6 +2345,7 @@ class _AffineRun:
         self._rt_shape_ok = None  # mnf_affine_half_rt_stack_supported, asked once
         self._rt_bwd_ok = None    # mnf_affine_half_bwd_rt_stack_supported, asked once
         self._rt_bwd_wide_ok = None  # mnf_affine_half_bwd_rt_wide_stack_supported, asked once
+        self._sample_ok = None    # mnf_affine_half_stack_sample_supported, asked once
         self._rt_now = False      # the call in flight trains on the run-time-shaped route (launch_grad -> _AffineRunFn)
         # the owner's switch (NormalizingFlow / FusedAffineStack .fuse_rt_training), copied here before every pass
         self.fuse_rt_training = False
@@ -2489,13 +2490,45 @@ class _AffineRun:
         if (not isinstance(x, Tensor) or not x.is_cuda or x.dim() != 2 or x.shape[0] == 0
                 or x.shape[1] != self.layers[0].dim or any(_wants_grad(f, x) for f in self.layers)):
             return None
+        return self.ready_for(x.shape[0], x.device)
+
+    def ready_for(self, rows: int, device):
+        """``ready`` for a no-grad (rows, dim) batch on ``device`` that need not exist: a seeded ``sample`` has no
+        input tensor, its rows are generated inside the launch."""
+        if rows <= 0:
+            return None
         if not self._unsupported and not any(f.force_generic for f in self.layers):
-            imgs = self.images(x.device)
+            imgs = self.images(device)
             if imgs[0] is not None:
                 return imgs
-        if self.rt_route(x.shape[0], x.device):
-            return ("rt", self.rt_flat(x.device))
+        if self.rt_route(rows, device):
+            return ("rt", self.rt_flat(device))
         return None
+
+    def launch_sample(self, seed: int, first_row: int, rows: int, device, images: tuple | None) -> Tensor | None:
+        """Rows ``first_row .. first_row + rows - 1`` of the seeded sample as ONE ``mnf_affine_half_stack_sample``
+        launch: the noise z[r, c] = z0_normal(seed, r, c) is generated in the stack kernel's registers, the layers are
+        applied in model order and only x is written.  ``images``: from ``ready_for``.  None when the run is not on
+        the split per-shape route or the library has no sample launch for the shape (the caller then materialises
+        the noise and runs the ordinary pass)."""
+        f0, n = self.layers[0], len(self.layers)
+        if images is None or isinstance(images[0], str) or images[1] is None or self._sample_ok is False:
+            return None
+        if self._sample_ok is None:
+            self._sample_ok = bool(_lib.load().mnf_affine_half_stack_sample_supported(f0.dim, len(f0.h_sizes), f0._hid, n))
+            if not self._sample_ok:
+                return None
+        y = torch.empty((rows, f0.dim), dtype=torch.float32, device=device)
+        par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
+        with torch.cuda.device(y.device):
+            rc = _lib.load().mnf_affine_half_stack_sample(
+                ctypes.c_uint64(seed), first_row, y.data_ptr(), images[0].data_ptr(), images[1].data_ptr(), par, n, rows,
+                f0.dim, len(f0.h_sizes), f0._hid, _stream())
+        if rc == _lib.MNF_ERR_UNSUPPORTED:
+            self._sample_ok = False
+            return None
+        _lib.check("mnf_affine_half_stack_sample", rc)
+        return y
 
     def usable(self, x) -> bool:
         return self.ready(x) is not None
@@ -2867,6 +2900,7 @@ class NormalizingFlow(nn.Module):
             if f is not self and hasattr(f, "invalidate"):
                 f.invalidate()
         self.__dict__.pop("_runs_cache", None)
+        self.__dict__.pop("_sample_run1", None)
 
     def _affine_runs(self) -> dict:
         """start index (model order) -> run object for every group of layers that goes out as one launch:
@@ -3076,10 +3110,29 @@ class StandardNormal:
             z.data_ptr(), None, lp.data_ptr(), None, z.shape[0], self.dim, _stream()))
         return lp
 
-    def sample(self, sample_shape=torch.Size()) -> Tensor:
+    def sample(self, sample_shape=torch.Size(), seed: int | None = None, first_row: int = 0) -> Tensor:
+        """``seed`` given: rows ``first_row .. first_row + n - 1`` of the counter-based stream z[r, c] =
+        z0_normal(seed, r, c) (``mnf_normal_rows``; tests/rng_reference.py restates it on the host) -- a pure function
+        of (seed, row, column), so chunks and row ranges of one seed are pieces of one sample.  Without a seed:
+        torch's generator, as before."""
         if isinstance(sample_shape, int):
             sample_shape = (sample_shape,)
-        return torch.randn(*sample_shape, self.dim, device=self.device)
+        if seed is None:
+            if first_row != 0:
+                raise ValueError("first_row names a row of the seeded stream: pass seed= as well")
+            return torch.randn(*sample_shape, self.dim, device=self.device)
+        shape = tuple(sample_shape)
+        if len(shape) != 1 or isinstance(shape[0], bool) or not isinstance(shape[0], int) or shape[0] < 0:
+            raise ValueError("a seeded sample is a block of rows of the stream: exactly one integer row count")
+        if isinstance(first_row, bool) or not isinstance(first_row, int) or first_row < 0:
+            raise ValueError("first_row must be a non-negative integer")
+        out = torch.empty((shape[0], self.dim), dtype=torch.float32, device=self.device)
+        if shape[0] > 0:
+            with torch.cuda.device(out.device):
+                _lib.check("mnf_normal_rows", _lib.load().mnf_normal_rows(
+                    ctypes.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), first_row, out.data_ptr(), shape[0], self.dim,
+                    _stream()))
+        return out
 
 
 class NormalizingFlowModel(NormalizingFlow):
@@ -3093,10 +3146,58 @@ class NormalizingFlowModel(NormalizingFlow):
         zs, _ = self._pass(x, True, last_only=True)  # z and only z: no intermediate is written
         return self.base.log_prob(zs[-1])
 
-    def sample(self, *num_samples: int) -> Tensor:
-        z = self.base.sample(*num_samples)
-        xs, _ = self.forward(z)
-        return xs[-1]
+    def sample(self, *num_samples: int, seed: int | None = None, first_row: int = 0) -> Tensor:
+        """Without ``seed``: the reference's sample (core.py:51-55) -- the base's draw from torch's generator, then
+        ``forward``.
+
+        ``sample(n, seed=s, first_row=r0)`` (StandardNormal base, no gradients): rows ``r0 .. r0 + n - 1`` of THE sample
+        of seed ``s``, x = forward(z) with z[r, c] = z0_normal(s, r, c) -- the library's counter-based normal stream
+        (``mnf_normal_rows`` materialises it, tests/rng_reference.py restates it on the host).  A pure function of
+        (seed, row, parameters): chunks and per-rank row ranges of one seed concatenate to the whole.  A model that is
+        one run of AffineHalfFlow layers on the split per-shape stack kernel draws the noise inside that kernel -- ONE
+        launch that reads no row tensor and writes only x (``ahf_split_stack_sample``); every other model materialises
+        the noise and runs the pass without intermediates.  Both routes compute the same sample."""
+        if seed is None:
+            if first_row != 0:
+                raise ValueError("first_row names a row of the seeded stream: pass seed= as well")
+            z = self.base.sample(*num_samples)
+            xs, _ = self.forward(z)
+            return xs[-1]
+        if not isinstance(self.base, StandardNormal):
+            raise ValueError("seeded sampling needs a StandardNormal base: the stream is defined for N(0, I)")
+        if len(num_samples) != 1 or isinstance(num_samples[0], bool) or not isinstance(num_samples[0], int) or num_samples[0] < 0:
+            raise ValueError("seeded sampling takes exactly one integer row count")
+        if isinstance(first_row, bool) or not isinstance(first_row, int) or first_row < 0:
+            raise ValueError("first_row must be a non-negative integer")
+        n, seed = num_samples[0], int(seed) & 0xFFFFFFFFFFFFFFFF
+        with torch.no_grad():
+            run = self._sample_run()
+            if run is not None and n > 0:
+                dev = self.base.device  # ("cuda" -> the current device, as the tensors of a pass name it: one image cache)
+                if dev.type == "cuda" and dev.index is None:
+                    dev = torch.device("cuda", torch.cuda.current_device())
+                x = run.launch_sample(seed, first_row, n, dev, run.ready_for(n, dev))
+                if x is not None:
+                    return x
+            z = self.base.sample((n,), seed=seed, first_row=first_row)
+            xs, _ = self._pass(z, False, last_only=True)  # (no intermediates where a run is fused)
+            return xs[-1]
+
+    def _sample_run(self) -> "_AffineRun | None":
+        """The model as ONE run of AffineHalfFlow layers (a single layer included: ``_affine_runs`` starts at two), or
+        None: mixed layers, run fusion switched off, per-launch event marks being collected."""
+        if not self.fuse_affine_runs or _NO_RUN_FUSION_ENV or self.layer_events is not None or len(self.flows) == 0:
+            return None
+        if len(self.flows) == 1:
+            f = self.flows[0]
+            if type(f) is not AffineHalfFlow:
+                return None
+            cached = self.__dict__.get("_sample_run1")
+            if cached is None or cached.layers[0] is not f:
+                cached = self.__dict__["_sample_run1"] = _AffineRun([f])
+            return cached
+        run = self._affine_runs().get(0)
+        return run if isinstance(run, _AffineRun) and len(run.layers) == len(self.flows) else None
 
     def graphed_log_prob(self, example: Tensor):
         """Capture one ``log_prob(x, return_sum=True)`` pass (every coupling kernel + the epilogue)
