@@ -114,6 +114,61 @@ def test_argument_checking_without_a_gpu(lib):
     assert lib.mnf_nsf_cl(p, p + 512, None, 0, p, None, None, 4, 32, 2000, 3.0, 0, 3, hid, 0, None) == -5  # K too large
     assert lib.mnf_rqs(p, p, p, p, p, p, 4, 1001, 3.0, 0, None) == -5
     assert lib.mnf_affine_half(p, p + 512, None, 0, p, None, None, 0, 64, 0, 0, 3, hid, 1, 1, 0, None) == 0  # empty batch
+    # the launch entries of the per-shape AffineHalfFlow and NSF_CL units: a null pointer and an odd dim are -1, a shape
+    # without a kernel or a misaligned row pointer -2, each answered before anything is launched
+    q, par = p + 512, int_array([0, 1])
+    wide, mixed, h8 = int_array([65, 65, 65]), int_array([24, 16, 24]), int_array([8, 8, 8])
+    stack = lib.mnf_affine_half_stack
+    assert stack(None, q, None, None, None, None, None, 0, p, None, par, 2, 4, 64, 0, 3, hid, None) == -1
+    assert stack(p, q, None, None, None, None, None, 0, p, None, par, 2, 4, 63, 0, 3, hid, None) == -1
+    assert stack(p, q, None, None, None, None, None, 0, p, None, par, 33, 4, 64, 0, 3, hid, None) == -1  # > 32 layers
+    assert stack(p, q, None, None, None, None, None, 0, p, None, par, 2, 4, 64, 0, 3, wide, None) == -2
+    assert stack(p, q, None, p, None, p, None, 0, p, None, par, 2, 4, 64, 0, 3, hid, None) == -2  # log-prob: split only
+    assert stack(p + 4, q, None, None, None, None, None, 0, p, None, par, 2, 4, 64, 0, 3, hid, None) == -2
+    sample = lib.mnf_affine_half_stack_sample
+    assert sample(1, 0, None, p, p, par, 2, 4, 64, 3, hid, None) == -1
+    assert sample(1, 0, q, p, p, par, 2, 4, 63, 3, hid, None) == -1
+    assert sample(1, 0, q, p, p, par, 2, 4, 64, 3, wide, None) == -2
+    assert sample(1, 0, q, p, p, par, 2, 4, 30, 3, hid, None) == -2  # a narrow half has no sample launch
+    assert sample(1, 0, q + 4, p, p, par, 2, 4, 64, 3, hid, None) == -2
+    bwd = lib.mnf_affine_half_bwd_mfma
+    assert bwd(None, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, None) == -1
+    assert bwd(p, q, None, q, q, p, p, 4, 63, 0, 0, 3, hid, None) == -1
+    assert bwd(p, q, None, q, q, p, p, 4, 64, 0, 0, 3, wide, None) == -2
+    assert bwd(p, q, None, q, q, p, p, 4, 130, 0, 0, 3, int_array([32, 32, 32]), None) == -2  # 24 slots only at d > 64
+    assert bwd(p + 4, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, None) == -2
+    tiles = lib.mnf_affine_half_bwd_mfma_tiles
+    assert tiles(p, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, p, -1, None) == -1
+    assert tiles(p, q, None, q, q, p, p, 4, 64, 0, 0, 3, wide, p, 1, None) == -2
+    det = lib.mnf_affine_half_bwd_mfma_det
+    assert det(p, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, None, 1 << 30, None) == -1
+    assert det(p, q, None, q, q, p, p, 4, 63, 0, 0, 3, hid, p, 1 << 30, None) == -1
+    assert det(p, q, None, q, q, p, p, 4, 64, 0, 0, 3, wide, p, 1 << 30, None) == -2
+    assert det(p + 4, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, p, 1, None) == -1  # the workspace is checked first
+    assert det(p + 4, q, None, q, q, p, p, 4, 64, 0, 0, 3, hid, p, 1 << 30, None) == -2
+    for fn, lead in ((lib.mnf_affine_half_bwd_split, (q, None)), (lib.mnf_affine_half_bwd_split_lp, (p, q))):
+        assert fn(p, *lead, q, q, p, p, 4, 64, 0, 0, 3, hid, p, None, 1, None, 0, None) == -1  # no cold list
+        assert fn(p, *lead, q, q, p, p, 4, 63, 0, 0, 3, hid, p, p, 1, None, 0, None) == -1
+        assert fn(p, *lead, q, q, p, p, 4, 64, 0, 0, 3, mixed, p, p, 1, None, 0, None) == -2  # equal widths only
+        assert fn(p, *lead, q, q, p, p, 4, 128, 0, 0, 3, hid, p, p, 1, None, 0, None) == -2
+        assert fn(p + 4, *lead, q, q, p, p, 4, 64, 0, 0, 3, hid, p, p, 1, None, 0, None) == -2
+    assert lib.mnf_affine_half_bwd_split_lp(p, None, q, q, q, p, p, 4, 64, 0, 0, 3, hid, p, p, 1, None, 0, None) == -1
+    fused = lib.mnf_nsf_cl_fused
+    assert fused(p, q, None, 0, p, p, None, 0.0, None, None, None, None, None, 4, 32, 8, 3.0, 0, 3, h8, None) == -1
+    assert fused(p, q, None, 0, p, p, p, 0.0, None, None, None, None, None, 4, 31, 8, 3.0, 0, 3, h8, None) == -1
+    assert fused(p, q, None, 0, p, p, p, 0.0, None, None, None, None, None, 4, 32, 4, 3.0, 0, 3, h8, None) == -2
+    assert fused(p, q, None, 0, p, p, p, 0.0, None, None, None, None, None, 4, 32, 10, 3.0, 0, 3, h8, None) == -2  # not fused
+    assert fused(p, q, None, 0, p, p, p, 0.0, None, None, None, None, None, 4, 24, 8, 3.0, 0, 3, h8, None) == -2  # narrow half
+    assert fused(p, q, None, 0, p, None, p, 0.0, None, None, None, None, None, 4, 32, 8, 3.0, 0, 3, h8, None) == -2  # fp32
+    assert fused(p + 4, q, None, 0, p, p, p, 0.0, None, None, None, None, None, 4, 32, 8, 3.0, 0, 3, h8, None) == -2
+    tile = lib.mnf_nsf_cl_bwd_tile
+    assert tile(p, q, q, None, q, q, p, p, 16, 32, 8, 3.0, 0, 3, h8, p, None, 1, p, 1 << 30, None) == -1  # no cold list
+    assert tile(p, q, q, None, q, q, p, p, 16, 31, 8, 3.0, 0, 3, h8, p, p, 1, p, 1 << 30, None) == -1
+    assert tile(p, q, q, None, q, q, p, p, 16, 32, 4, 3.0, 0, 3, h8, p, p, 1, p, 1 << 30, None) == -2
+    assert tile(p, q, q, None, q, q, p, p, 16, 32, 8, 3.0, 0, 3, hid, p, p, 1, p, 1 << 30, None) == -2  # <= 16 units
+    assert tile(p + 4, q, q, None, q, q, p, p, 16, 32, 8, 3.0, 0, 3, h8, p, p, 0, p, 0, None) == -2  # alignment first
+    assert tile(p, q, q, None, q, q, p, p, 16, 32, 8, 3.0, 0, 3, h8, p, p, 0, p, 1 << 30, None) == -1  # cold list too short
+    assert tile(p, q, q, None, q, q, p, p, 16, 32, 8, 3.0, 0, 3, h8, p, p, 1, p, 0, None) == -1  # workspace too small
 
 
 def test_product_path_refuses_cpu_tensors():

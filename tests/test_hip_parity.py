@@ -225,6 +225,21 @@ def test_affine_half_mfma_shape_matrix(amd, O, dim, hid, kernel):
             y, ld = f.forward(cuda(x), inverse=inverse)
             assert_close(y, ref_y, RTOL, "y")
             assert_close(ld, ref_ld, RTOL, "ld")
+    if hid > 32:
+        return
+    # The same layer as a one-layer FusedAffineStack, 1,000 rows: the stack launch at n_layers = 1 -- the only route to the
+    # split stack kernel's full-tile instantiations at hidden width 32 and d <= 64 (a longer run of that shape goes layer by
+    # layer) and, on the fp32 request, to the fp32 stack kernel's (d = 32 and 64 at hidden widths 16 and 24)
+    x = recipes.gaussian(92 + dim, 1000, dim)
+    fused = amd.FusedAffineStack([ahf_module(amd, sd, dim, True, kernel, h_sizes=h_sizes)]).to(DEV)
+    want = "ahf_split_stack" if kernel == "split" else "ahf_stack_fp32" if dim <= 64 and hid <= 24 else None
+    with torch.no_grad():
+        for inverse in (False, True):
+            ref_y, ref_ld = O.affine_half(x, sd, True, inverse)
+            y, ld = (fused.inverse if inverse else fused.forward)(cuda(x))
+            assert want is None or amd.last_kernel() == want, (amd.last_kernel(), want)
+            assert_close(y, ref_y, RTOL, "one-layer stack y")
+            assert_close(ld, ref_ld, RTOL, "one-layer stack ld")
 
 
 @pytest.mark.parametrize("kernel", ["split", "fp32"])
@@ -1352,7 +1367,9 @@ def g10_padded_shapes(amd, golden, kernel):
 
 @pytest.mark.parametrize("kernel", ["split", "fp32"])
 @pytest.mark.parametrize("dim,K,n_h", [(32, 8, 8), (32, 8, 16), (32, 5, 8), (32, 5, 16), (64, 8, 8), (64, 5, 8), (64, 8, 16),
-                                       (32, 8, 12), (64, 5, 3), (32, 5, 1), (32, 10, 8), (32, 10, 16), (16, 10, 8)])
+                                       (32, 8, 12), (64, 5, 3), (32, 5, 1), (32, 10, 8), (32, 10, 16), (16, 10, 8),
+                                       # a half narrower than its tile, at the shapes no other case runs that variant at
+                                       (24, 5, 16), (24, 10, 16), (40, 5, 8), (40, 5, 16), (40, 8, 16)])
 def test_nsf_cl_mfma_shape_matrix(amd, O, dim, K, n_h, kernel):
     """Every (dim, K, n_h) triple with an MFMA spline kernel -- incl. the reference's default K = 5 and the n_h = 16 of
     its tests at both dims; an n_h other than 8 / 16 runs at the next one up (n_h > 16: the run-time-shaped kernel,
@@ -1363,7 +1380,8 @@ def test_nsf_cl_mfma_shape_matrix(amd, O, dim, K, n_h, kernel):
     f = select_kernel(f.to(DEV), kernel)
     assert f._packed(torch.device(DEV, 0))[1] is not None
     assert (f._split_image(torch.device(DEV, 0)) is not None) == (kernel == "split" and n_h >= 4)
-    x = recipes.gaussian(1501 + dim, 531, dim, scale=1.5)
+    narrow = dim in (24, 40)  # the narrow-half cases at tile halves 16 and 32: 1,000 rows, and the split launch must be the per-shape kernel's
+    x = recipes.gaussian(1501 + dim, 1000 if narrow else 531, dim, scale=1.5)
     sd64 = {k: v.double() for k, v in sd.items()}
     for inverse in (False, True):
         ref_y, ref_ld = O.nsf_cl(x, sd, K, 3.0, inverse)
@@ -1372,12 +1390,14 @@ def test_nsf_cl_mfma_shape_matrix(amd, O, dim, K, n_h, kernel):
         # between two correct fp32 evaluations)
         y64, ld64 = O.nsf_cl(x.double(), sd64, K, 3.0, inverse)
         y, ld = (f.inverse if inverse else f.forward)(cuda(x))
+        if narrow and kernel == "split":
+            assert amd.last_kernel() == "nsf_mfma_split", amd.last_kernel()
         # (tame nn.Linear-scale weights: the head-room is capped at 5e-5, helpers.MAX_WIDENING)
         assert_parity(y, ref_y.numpy(), y64.numpy(), f"nsf shape ({dim},{K},{n_h}) {kernel} inv={inverse} y")
         assert_parity(ld, ref_ld.numpy(), ld64.numpy(), f"nsf shape ({dim},{K},{n_h}) {kernel} inv={inverse} ld")
 
 
-@pytest.mark.parametrize("dim,K,n_h", [(64, 8, 8), (64, 5, 8), (64, 8, 16), (32, 5, 8), (32, 5, 16)])
+@pytest.mark.parametrize("dim,K,n_h", [(64, 8, 8), (64, 5, 8), (64, 8, 16), (32, 5, 8), (32, 5, 16), (32, 8, 16)])
 def test_spline_block_run_at_other_shapes(amd, dim, K, n_h):
     """[ActNorm, Glow, NSF_CL] blocks as one launch each for the other MFMA spline shapes (d = 64; K = 5): same
     tensors, log_det and log-prob as running the nine layers one by one."""
@@ -1391,11 +1411,12 @@ def test_spline_block_run_at_other_shapes(amd, dim, K, n_h):
         nsf.load_state_dict(recipes.nsf_cl_params(1600 + dim + i, dim, K, n_h))
         flows += [a, amd.Glow(dim), nsf]
     model = amd.NormalizingFlowModel(amd.StandardNormal(dim), flows).to(DEV)
-    x = cuda(recipes.gaussian(1601 + dim, 700, dim))
+    x = cuda(recipes.gaussian(1601 + dim, 1000 if (dim, K, n_h) == (32, 8, 16) else 700, dim))
     with torch.no_grad():
         for direction in ("inverse", "forward"):
             model.fuse_affine_runs = True
             zs_f, ld_f = getattr(model, direction)(x)
+            assert amd.last_kernel() == "nsf_block_split", amd.last_kernel()
             assert zs_f[1].data_ptr() + zs_f[1].numel() * 4 == zs_f[2].data_ptr()  # one launch, one buffer
             model.fuse_affine_runs = False
             zs_u, ld_u = getattr(model, direction)(x)

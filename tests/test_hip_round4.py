@@ -229,15 +229,18 @@ def test_wide_mnf_linear_sees_fused_optimizer_updates(amd, graphed):
     assert_close(after, want, 1e-5, "wide layer after fused optimizer steps vs a fresh layer with the same parameters")
 
 
-@pytest.mark.parametrize("rows,n_layers,x_scale,s_gain", [(1007, 9, 1.0, 2.0), (4096, 9, 1.0, 2.0), (1007, 2, 2500.0, 0.002)])
-def test_log_prob_training_node_matches_the_unfused_route(amd, rows, n_layers, x_scale, s_gain):
+@pytest.mark.parametrize("rows,n_layers,x_scale,s_gain,dim,hid",
+                         [(1007, 9, 1.0, 2.0, 64, 24), (4096, 9, 1.0, 2.0, 64, 24), (1007, 2, 2500.0, 0.002, 64, 24),
+                          (1007, 3, 1.0, 2.0, 32, 24), (1007, 3, 1.0, 2.0, 32, 16), (1007, 3, 1.0, 2.0, 64, 16)],
+                         ids=["1007-9-1.0-2.0", "4096-9-1.0-2.0", "1007-2-2500.0-0.002", "d32_h24", "d32_h16", "d64_h16"])
+def test_log_prob_training_node_matches_the_unfused_route(amd, rows, n_layers, x_scale, s_gain, dim, hid):
     """`-model.log_prob(x).mean()` under a standard-normal base with the whole model one run of AffineHalfFlow layers:
     ONE autograd node from x to log p (the stack kernel's log-prob epilogue forward; the last layer's cotangents formed
     inside mnf_affine_half_bwd_split_lp backward) against the unfused route (log_det + base.log_prob(z) with its own
     autograd link, validated against the float64 oracle by tests/test_hip_autograd.py).  The third case scales x
     beyond the split range (two layers, |x| up to ~1e4 > 8192): most 16-row tiles go to the fp32 fix-up pass, which
-    then reads the grad_y rows the split kernel left in its scratch buffer."""
-    dim = 64
+    then reads the grad_y rows the split kernel left in its scratch buffer.  The last three: the split gradient kernel's
+    other shapes (d = 32, hidden width 16)."""
     flows_mod = amd.flows
     floor, flows_mod._dispatch.BWD_SPLIT_MIN_ROWS = flows_mod._dispatch.BWD_SPLIT_MIN_ROWS, 0
     try:
@@ -245,8 +248,8 @@ def test_log_prob_training_node_matches_the_unfused_route(amd, rows, n_layers, x
         for fused in (True, False):
             layers = []
             for i in range(n_layers):
-                f = amd.AffineHalfFlow(dim, parity=bool(i % 2))
-                f.load_state_dict(recipes.affine_half_params(1000 + i, dim, s_last_gain=s_gain))
+                f = amd.AffineHalfFlow(dim, parity=bool(i % 2), h_sizes=(hid,) * 3)
+                f.load_state_dict(recipes.affine_half_params(1000 + i, dim, h_sizes=(hid,) * 3, s_last_gain=s_gain))
                 layers.append(f)
             model = amd.NormalizingFlowModel(amd.StandardNormal(dim), layers).to(DEV)
             x = (recipes.gaussian(77, rows, dim) * x_scale).to(DEV).requires_grad_(True)

@@ -31,7 +31,8 @@ pytestmark = pytest.mark.gpu
 
 SEEDS = [R.Z0_XOR, 0x123456789ABCDEF0]  # (0x5bd1e995: element (0, 0) has h1 == 0, the largest radius; seed >> 32 != 0)
 GROUP_ROWS = 128
-SHAPES = [(64, 24, 9), (32, 16, 2), (32, 24, 1), (128, 24, 3), (256, 24, 2), (128, 32, 2)]  # (dim, hidden, layers)
+SHAPES = [(64, 24, 9), (32, 16, 2), (32, 24, 1), (128, 24, 3), (256, 24, 2), (128, 32, 2),  # (dim, hidden, layers)
+          (64, 16, 2), (32, 32, 1), (64, 32, 1)]  # (hidden width 32 at d <= 64: one layer, else layer by layer)
 ROWS = [1, 15, 16, 17, GROUP_ROWS - 1, GROUP_ROWS, GROUP_ROWS + 1, 4099]
 FAMILY = "ahf_split_stack_sample"
 

@@ -555,9 +555,6 @@ static void build_bwd_index(int32_t* idx, int rh, const int* hs, bool has_s, boo
         if (16 * g + i < rh && present[nn]) fb[t * 16 + i] = net[nn].b_off[3] + 16 * g + i;
 }
 
-// shapes: 16, 24 or 32 hidden-unit slots at tile halves 16, 32 (d <= 64; narrower halves and layers padded), 24 at 64, 128
-#define MNF_AHF_BWD_SHAPES(X) X(16, 24) X(32, 24) X(16, 16) X(32, 16) X(64, 24) X(16, 32) X(32, 32) X(128, 24)
-
 // second stage of the deterministic flush: entry i of the flush tables (weights, then biases) += the blocks' entries i, in
 // block order; every parameter appears in exactly one entry
 __global__ void __launch_bounds__(256)
@@ -572,73 +569,74 @@ ahf_bwd_mfma_reduce_kernel(const float* __restrict__ partials, int n_blocks, int
   grad_flat[dst] += s;
 }
 
+// ---------------------------------------------------------------- host: the shape table
+using BwdKernel = void (*)(const float*, const float*, const float*, float*, float*, const float*, const int32_t*, int64_t,
+                           int, const int32_t*, int, int);
+struct BwdRow {
+  int H, HID, waves;
+  int index_ints, image_floats, red_floats;  // red_floats: the flush tables' entries = a workgroup's block of partial sums
+  size_t lds_bytes;
+  void (*build_index)(int32_t*, int, const int*, bool, bool);
+  BwdKernel kernel[2][2];  // [full tiles][inverse, forward]
+  DeviceMemo cus[2];       // [full tiles], per device: CU count once the dynamic-LDS attribute is set there, -1 if it cannot be
+};
 template <int H, int HID>
-static int64_t bwd_blocks(int64_t rows) {
+static BwdRow make_row() {
   using S = BwdShape<H, HID>;
-  const int cus = device_cus(current_device());
-  const int64_t n_tiles = (rows + 15) / 16, blocks = (n_tiles + S::WAVES - 1) / S::WAVES;
-  return blocks > cus ? cus : blocks;
+  return {H, HID, S::WAVES, S::INDEX_INTS, S::IMAGE_FLOATS, S::DW_TILES * 256 + S::DB_TILES * 16,
+          S::LDS_FLOATS * sizeof(float), build_bwd_index<H, HID>,
+          {{ahf_bwd_mfma_kernel<H, HID, true, true>, ahf_bwd_mfma_kernel<H, HID, false, true>},
+           {ahf_bwd_mfma_kernel<H, HID, true, false>, ahf_bwd_mfma_kernel<H, HID, false, false>}}, {}};
+}
+// 16, 24 or 32 hidden-unit slots at tile halves 16, 32 (d <= 64; narrower halves and layers padded), 24 at 64, 128
+static BwdRow g_rows[] = {make_row<16, 24>(), make_row<32, 24>(), make_row<16, 16>(), make_row<32, 16>(),
+                          make_row<64, 24>(), make_row<16, 32>(), make_row<32, 32>(), make_row<128, 24>()};
+
+// The row a layer of `dim` columns runs at, or null.  The half is padded to its tile (h = dim / 2 < row->H: a ragged half),
+// the three hidden layers to 16, 24 or 32 slots, whichever holds the widest (narrower layers get structural-zero units: zero
+// operands, LeakyReLU(0) = 0, no flush).
+static BwdRow* find_row(int dim, int n_hidden, const int* hidden) {
+  if (n_hidden != 3 || !hidden || dim < 2 || (dim & 1)) return nullptr;
+  int mx = 0;
+  for (int i = 0; i < 3; ++i) mx = hidden[i] > mx ? hidden[i] : mx;
+  int hid = mx <= 16 ? 16 : mx <= 24 ? 24 : mx <= 32 ? 32 : 0;
+  const int h = dim / 2, ph = h <= 16 ? 16 : h <= 32 ? 32 : h <= 64 ? 64 : h <= 128 ? 128 : 0;
+  if (hid == 0) return nullptr;
+  if (ph >= 64) hid = hid <= 24 ? 24 : 0;  // (the 64- and 128-column tiles exist with 24 hidden units only)
+  for (BwdRow& r : g_rows)
+    if (ph == r.H && hid == r.HID) return &r;
+  return nullptr;
 }
 
-template <int H, int HID, bool RAG>
-static int launch_bwd(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
-                      const float* flat, const int32_t* index, int64_t rows, int parity, int inverse,
-                      const int32_t* tile_list, int list_capacity, int real_h, hipStream_t stream,
-                      float* partials = nullptr) {
-  using S = BwdShape<H, HID>;
-  constexpr size_t lds_bytes = S::LDS_FLOATS * sizeof(float);
-  static DeviceMemo memo;  // per device: CU count once the dynamic-LDS attribute is set there, -1 if it cannot be
-  const int cus = memo.get([](int dev) {
-    const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_bwd_mfma_kernel<H, HID, true, RAG>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_bwd_mfma_kernel<H, HID, false, RAG>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess;
-    return ok ? device_cus(dev) : -1;
-  });
+static int64_t bwd_blocks(const BwdRow& r, int64_t rows, int cus) {
+  const int64_t n_tiles = (rows + 15) / 16, blocks = (n_tiles + r.waves - 1) / r.waves;
+  return blocks > cus ? cus : blocks;  // one persistent workgroup per CU (LDS bound)
+}
+
+static int launch_bwd(BwdRow& r, const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                      const float* flat, const int32_t* index, int64_t rows, int dim, int parity, int inverse,
+                      const int32_t* tile_list, int list_capacity, hipStream_t stream, float* partials = nullptr) {
+  const bool full = dim == 2 * r.H;  // (a ragged half: element-wise row accesses, no alignment condition)
+  if (full && !aligned16(x, grad_y, grad_x)) return MNF_ERR_UNSUPPORTED;
+  const int cus = dynamic_lds_memo(r.cus[full], r.lds_bytes, r.kernel[full], 2, device_cus);
   if (cus <= 0) return MNF_ERR_UNSUPPORTED;
-  const int64_t n_tiles = (rows + 15) / 16;
-  int64_t blocks = (n_tiles + S::WAVES - 1) / S::WAVES;
-  if (blocks > cus) blocks = cus;  // one persistent workgroup per CU (LDS bound)
+  int64_t blocks = bwd_blocks(r, rows, cus);
   // (a fix-up pass gets the full grid too: the list is usually empty and every workgroup returns at once, but it may
   //  also name every tile)
   // MNF_DETERMINISTIC: the list in ascending order and ONE workgroup -- its waves take the tiles in list order and add up
   // in wave order (mnf_host.h det_sort_ids_async)
   if (tile_list && !partials && deterministic() &&
-      det_sort_ids_async(const_cast<int32_t*>(tile_list) + 1, tile_list, list_capacity, n_tiles, stream) == MNF_OK)
+      det_sort_ids_async(const_cast<int32_t*>(tile_list) + 1, tile_list, list_capacity, (rows + 15) / 16, stream) == MNF_OK)
     blocks = 1;
-  const dim3 grid((unsigned)blocks), block(S::WAVES * 64);
   if (!tile_list) tag_kernel("ahf_bwd_mfma_fp32");  // (as the split kernel's fix-up pass it keeps that kernel's name)
-  if (inverse)
-    hipLaunchKernelGGL((ahf_bwd_mfma_kernel<H, HID, true, RAG>), grid, block, lds_bytes, stream, x, grad_y, grad_ld,
-                       grad_x, partials ? partials : grad_flat, flat, index, rows, parity, tile_list,
-                       partials ? kBwdBlocksMode : list_capacity, real_h);
-  else
-    hipLaunchKernelGGL((ahf_bwd_mfma_kernel<H, HID, false, RAG>), grid, block, lds_bytes, stream, x, grad_y, grad_ld,
-                       grad_x, partials ? partials : grad_flat, flat, index, rows, parity, tile_list,
-                       partials ? kBwdBlocksMode : list_capacity, real_h);
+  hipLaunchKernelGGL(r.kernel[full][inverse ? 0 : 1], dim3((unsigned)blocks), dim3(r.waves * 64), r.lds_bytes, stream, x,
+                     grad_y, grad_ld, grad_x, partials ? partials : grad_flat, flat, index, rows, parity != 0, tile_list,
+                     partials ? kBwdBlocksMode : list_capacity, dim / 2);
   if (int rc = check_launch()) return rc;
   if (!partials || !grad_flat) return MNF_OK;
-  constexpr int RED = S::DW_TILES * 256 + S::DB_TILES * 16;
-  hipLaunchKernelGGL(ahf_bwd_mfma_reduce_kernel, dim3((RED + 255) / 256), dim3(256), 0, stream, partials, (int)blocks, RED,
-                     index + S::IMAGE_FLOATS, grad_flat);
+  hipLaunchKernelGGL(ahf_bwd_mfma_reduce_kernel, dim3((r.red_floats + 255) / 256), dim3(256), 0, stream, partials,
+                     (int)blocks, r.red_floats, index + r.image_floats, grad_flat);
   return check_launch();
-}
-
-// the tile half width a layer of `dim` columns runs at (0: none): halves narrower than a tile are padded
-static int bwd_padded_half(int dim) {
-  if (dim < 2 || (dim & 1)) return 0;
-  const int h = dim / 2;
-  return h <= 16 ? 16 : h <= 32 ? 32 : h <= 64 ? 64 : h <= 128 ? 128 : 0;
-}
-
-// the hidden width the kernel runs three hidden layers of widths hidden[0..2] at: 16, 24 or 32, whichever holds the widest
-// (narrower layers get structural-zero units: zero operands, LeakyReLU(0) = 0, no flush); false: none
-static bool bwd_uniform3(int n_hidden, const int* hidden, int& hid) {
-  if (n_hidden != 3 || !hidden) return false;
-  int mx = 0;
-  for (int i = 0; i < 3; ++i) mx = hidden[i] > mx ? hidden[i] : mx;
-  hid = mx <= 16 ? 16 : mx <= 24 ? 24 : mx <= 32 ? 32 : 0;
-  return hid != 0;
 }
 
 }  // namespace mnf
@@ -646,33 +644,18 @@ static bool bwd_uniform3(int n_hidden, const int* hidden, int& hid) {
 extern "C" {
 
 int64_t mnf_affine_half_bwd_index_ints(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift) {
-  int hid = 0;
-  if ((!has_scale && !has_shift) || !mnf::hidden_ok(n_hidden, hidden) || !mnf::bwd_uniform3(n_hidden, hidden, hid))
-    return 0;
-  const int ph = mnf::bwd_padded_half(dim);
-  if (ph >= 64) hid = hid <= 24 ? 24 : 0;  // (the 64- and 128-column tiles exist with 24 hidden units only)
-#define X(HH, HD) \
-  if (ph == HH && hid == HD) return mnf::BwdShape<HH, HD>::INDEX_INTS;
-  MNF_AHF_BWD_SHAPES(X)
-#undef X
-  return 0;
+  if ((!has_scale && !has_shift) || !mnf::hidden_ok(n_hidden, hidden)) return 0;
+  const mnf::BwdRow* r = mnf::find_row(dim, n_hidden, hidden);
+  return r ? r->index_ints : 0;
 }
 
 int mnf_affine_half_bwd_index(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                               int32_t* idx_host) {
-  int hid = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if ((!has_scale && !has_shift) || !mnf::bwd_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int ph = mnf::bwd_padded_half(dim);
-  if (ph >= 64) hid = hid <= 24 ? 24 : 0;  // (the 64- and 128-column tiles exist with 24 hidden units only)
-#define X(HH, HD)                                       \
-  if (ph == HH && hid == HD) {                          \
-    mnf::build_bwd_index<HH, HD>(idx_host, dim / 2, hidden, has_scale != 0, has_shift != 0);    \
-    return MNF_OK;                                      \
-  }
-  MNF_AHF_BWD_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::BwdRow* r = has_scale || has_shift ? mnf::find_row(dim, n_hidden, hidden) : nullptr;
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_index(idx_host, dim / 2, hidden, has_scale != 0, has_shift != 0);
+  return MNF_OK;
 }
 
 int mnf_affine_half_bwd_mfma(const float* x, const float* grad_y, const float* grad_ld, float* grad_x,
@@ -686,75 +669,34 @@ int mnf_affine_half_bwd_mfma_tiles(const float* x, const float* grad_y, const fl
                                    float* grad_flat, const float* flat, const int32_t* index_dev, int64_t rows, int dim,
                                    int parity, int inverse, int n_hidden, const int* hidden, const int32_t* tile_list,
                                    int list_capacity, void* stream) {
-  int hid = 0;
   if (list_capacity < 0) return MNF_ERR_INVALID_ARG;
   if (!x || !grad_x || !flat || !index_dev || rows < 0 || dim < 2 || (dim & 1) || !mnf::hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (!mnf::bwd_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int ph = mnf::bwd_padded_half(dim);
-  if (ph >= 64) hid = hid <= 24 ? 24 : 0;  // (the 64- and 128-column tiles exist with 24 hidden units only)
-  const bool ragged = ph != dim / 2;  // (element-wise row accesses: no alignment condition)
-  if (!ragged &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15))
-    return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                                                                      \
-  if (ph == HH && hid == HD)                                                                                           \
-    return ragged ? mnf::launch_bwd<HH, HD, true>(x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows,       \
-                                                  parity != 0, inverse != 0, tile_list, list_capacity, dim / 2,        \
-                                                  (hipStream_t)stream)                                                 \
-                  : mnf::launch_bwd<HH, HD, false>(x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows,      \
-                                                   parity != 0, inverse != 0, tile_list, list_capacity, dim / 2,       \
-                                                   (hipStream_t)stream);
-  MNF_AHF_BWD_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  mnf::BwdRow* r = mnf::find_row(dim, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  return mnf::launch_bwd(*r, x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows, dim, parity, inverse, tile_list,
+                         list_capacity, (hipStream_t)stream);
 }
 
 int64_t mnf_affine_half_bwd_mfma_workspace(int64_t rows, int dim, int n_hidden, const int* hidden) {
-  int hid = 0;
-  if (rows < 1 || dim < 2 || (dim & 1) || !mnf::hidden_ok(n_hidden, hidden) || !mnf::bwd_uniform3(n_hidden, hidden, hid))
-    return 0;
-  const int ph = mnf::bwd_padded_half(dim);
-  if (ph >= 64) hid = hid <= 24 ? 24 : 0;
-#define X(HH, HD) \
-  if (ph == HH && hid == HD) \
-    return mnf::bwd_blocks<HH, HD>(rows) * (mnf::BwdShape<HH, HD>::DW_TILES * 256 + mnf::BwdShape<HH, HD>::DB_TILES * 16);
-  MNF_AHF_BWD_SHAPES(X)
-#undef X
-  return 0;
+  const mnf::BwdRow* r = rows < 1 || !mnf::hidden_ok(n_hidden, hidden) ? nullptr : mnf::find_row(dim, n_hidden, hidden);
+  return r ? mnf::bwd_blocks(*r, rows, mnf::device_cus(mnf::current_device())) * r->red_floats : 0;
 }
 
 int mnf_affine_half_bwd_mfma_det(const float* x, const float* grad_y, const float* grad_ld, float* grad_x,
                                  float* grad_flat, const float* flat, const int32_t* index_dev, int64_t rows, int dim,
                                  int parity, int inverse, int n_hidden, const int* hidden, float* workspace,
                                  int64_t workspace_floats, void* stream) {
-  int hid = 0;
   if (!x || !grad_x || !flat || !index_dev || !workspace || rows < 0 || dim < 2 || (dim & 1) ||
       !mnf::hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (!mnf::bwd_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int64_t need = mnf_affine_half_bwd_mfma_workspace(rows, dim, n_hidden, hidden);
-  if (need == 0) return MNF_ERR_UNSUPPORTED;
-  if (workspace_floats < need) return MNF_ERR_INVALID_ARG;
-  const int ph = mnf::bwd_padded_half(dim);
-  if (ph >= 64) hid = hid <= 24 ? 24 : 0;
-  const bool ragged = ph != dim / 2;
-  if (!ragged &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x)) & 15))
-    return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                                                                       \
-  if (ph == HH && hid == HD)                                                                                            \
-    return ragged ? mnf::launch_bwd<HH, HD, true>(x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows,        \
-                                                  parity != 0, inverse != 0, nullptr, 0, dim / 2, (hipStream_t)stream, \
-                                                  workspace)                                                            \
-                  : mnf::launch_bwd<HH, HD, false>(x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows,       \
-                                                   parity != 0, inverse != 0, nullptr, 0, dim / 2, (hipStream_t)stream,\
-                                                   workspace);
-  MNF_AHF_BWD_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  mnf::BwdRow* r = mnf::find_row(dim, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  if (workspace_floats < mnf_affine_half_bwd_mfma_workspace(rows, dim, n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
+  return mnf::launch_bwd(*r, x, grad_y, grad_ld, grad_x, grad_flat, flat, index_dev, rows, dim, parity, inverse, nullptr, 0,
+                         (hipStream_t)stream, workspace);
 }
 
 }  // extern "C"

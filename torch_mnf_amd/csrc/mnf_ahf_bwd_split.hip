@@ -936,95 +936,88 @@ static int build_bwd_split_index(int32_t* idx) {
   return op == S::N_OPS + B::T_OPS ? MNF_OK : MNF_ERR_INVALID_ARG;
 }
 
-template <int H, int HID>
-static int launch_bwd_split(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
-                            const uint32_t* image, const int32_t* index, int64_t rows, int parity, int inverse,
-                            const float* scale_dev, int32_t* cold_list, int cold_capacity, float* workspace,
-                            int64_t workspace_floats, hipStream_t stream, const float* lp_grad = nullptr,
-                            float* gy_scratch = nullptr) {
-  using B = BwdSplitShape<H, HID>;
-  using Kernel = void (*)(const float*, const float*, const float*, float*, float*, const uint32_t*, const int32_t*, int64_t,
+// ---------------------------------------------------------------- host: the shape table
+using BsKernel = void (*)(const float*, const float*, const float*, float*, float*, const uint32_t*, const int32_t*, int64_t,
                           int, const float*, int32_t*, int, float*, const float*, float*);
-  static constexpr size_t lds_bytes = B::LDS_WORDS * sizeof(uint32_t);
-  const Kernel all[4] = {ahf_bwd_split_kernel<H, HID, true, false>, ahf_bwd_split_kernel<H, HID, false, false>,
-                         ahf_bwd_split_kernel<H, HID, true, true>, ahf_bwd_split_kernel<H, HID, false, true>};
-  static DeviceMemo memo;
-  const int cus = memo.get([&](int dev) {
-    bool ok = true;
-    for (int k = 0; k < 4; ++k)
-      ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(all[k]), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)lds_bytes) == hipSuccess;
-    return ok ? device_cus(dev) : -1;
-  });
+struct BsRow {
+  int H, HID;
+  int64_t split_words, plain_words, red_floats;
+  int flush_offset;  // where the flush tables start in the index (behind the fp32 gradient kernel's operand entries)
+  size_t lds_bytes;
+  int (*build_index)(int32_t*);
+  BsKernel kernel[4];  // [2 * lp + (inverse ? 0 : 1)]
+  DeviceMemo cus;      // per device: CU count once the dynamic-LDS attribute is set there, -1 if it cannot be
+};
+template <int H, int HID>
+static BsRow make_row() {
+  using B = BwdSplitShape<H, HID>;
+  return {H, HID, B::SPLIT_WORDS, B::PLAIN_WORDS, B::RED_FLOATS, B::F::IMAGE_FLOATS, B::LDS_WORDS * sizeof(uint32_t),
+          build_bwd_split_index<H, HID>,
+          {ahf_bwd_split_kernel<H, HID, true, false>, ahf_bwd_split_kernel<H, HID, false, false>,
+           ahf_bwd_split_kernel<H, HID, true, true>, ahf_bwd_split_kernel<H, HID, false, true>}, {}};
+}
+// the shapes of the fp32 gradient kernel at d <= 64 and hidden widths 16 and 24
+static BsRow g_rows[] = {make_row<16, 24>(), make_row<32, 24>(), make_row<16, 16>(), make_row<32, 16>()};
+
+// The row of a layer, or null: full tiles and three hidden layers of exactly the row's width.
+static BsRow* find_row(int dim, int n_hidden, const int* hidden) {
+  if (n_hidden != 3 || !hidden || hidden[1] != hidden[0] || hidden[2] != hidden[0]) return nullptr;
+  for (BsRow& r : g_rows)
+    if (dim == 2 * r.H && hidden[0] == r.HID) return &r;
+  return nullptr;
+}
+
+static int64_t bwd_split_blocks(int64_t rows, int cus) {
+  const int64_t n_tiles = (rows + 15) / 16, blocks = (n_tiles + kBsWaves - 1) / kBsWaves;
+  return blocks > cus ? cus : blocks;  // one persistent workgroup per CU (one wave per SIMD: the whole register file)
+}
+
+static int launch_bwd_split(const float* x, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
+                            const void* image, const int32_t* index, int64_t rows, int dim, int parity, int inverse,
+                            int n_hidden, const int* hidden, const float* scale_dev, int32_t* cold_list, int cold_capacity,
+                            float* workspace, int64_t workspace_floats, hipStream_t stream, const float* lp_grad = nullptr,
+                            float* gy_scratch = nullptr) {
+  BsRow* r = find_row(dim, n_hidden, hidden);
+  if (!r || !aligned16(x, grad_y, gy_scratch, grad_x, image)) return MNF_ERR_UNSUPPORTED;
+  const int cus = dynamic_lds_memo(r->cus, r->lds_bytes, r->kernel, 4, device_cus);
   if (cus <= 0) return MNF_ERR_UNSUPPORTED;
-  const int64_t n_tiles = (rows + 15) / 16;
-  int64_t blocks = (n_tiles + kBsWaves - 1) / kBsWaves;
-  if (blocks > cus) blocks = cus;  // one persistent workgroup per CU (one wave per SIMD: the whole register file)
-  const dim3 grid((unsigned)blocks), block(kBsWaves * 64);
-  float* partials = (grad_flat && workspace && workspace_floats >= blocks * B::RED_FLOATS) ? workspace : nullptr;
+  const int64_t blocks = bwd_split_blocks(rows, cus);
+  float* partials = (grad_flat && workspace && workspace_floats >= blocks * r->red_floats) ? workspace : nullptr;
   tag_kernel("ahf_bwd_split");
-  hipLaunchKernelGGL(all[(lp_grad ? 2 : 0) + (inverse ? 0 : 1)], grid, block, lds_bytes, stream, x, grad_y, grad_ld, grad_x,
-                     grad_flat, image, index, rows, parity, scale_dev, cold_list, cold_capacity, partials, lp_grad,
-                     gy_scratch);
+  hipLaunchKernelGGL(r->kernel[(lp_grad ? 2 : 0) + (inverse ? 0 : 1)], dim3((unsigned)blocks), dim3(kBsWaves * 64),
+                     r->lds_bytes, stream, x, grad_y, grad_ld, grad_x, grad_flat,
+                     static_cast<const uint32_t*>(image), index, rows, parity != 0, scale_dev, cold_list, cold_capacity,
+                     partials, lp_grad, gy_scratch);
   if (partials)
-    hipLaunchKernelGGL(ahf_bwd_reduce_kernel, dim3((B::RED_FLOATS + 31) / 32), dim3(256), 0, stream, partials, (int)blocks,
-                       (int)B::RED_FLOATS, index + B::F::IMAGE_FLOATS, grad_flat, scale_dev, cold_list);
+    hipLaunchKernelGGL(ahf_bwd_reduce_kernel, dim3((unsigned)((r->red_floats + 31) / 32)), dim3(256), 0, stream, partials,
+                       (int)blocks, (int)r->red_floats, index + r->flush_offset, grad_flat, scale_dev, cold_list);
   return check_launch();
 }
 
-static bool bwd_split_uniform3(int n_hidden, const int* hidden, int& hid) {
-  if (n_hidden != 3 || !hidden) return false;
-  hid = hidden[0];
-  return hidden[1] == hid && hidden[2] == hid;
-}
-
 }  // namespace mnf
-
-// shapes: those of the fp32 gradient kernel
-#define MNF_AHF_BWD_SPLIT_SHAPES(X) X(16, 24) X(32, 24) X(16, 16) X(32, 16)
 
 extern "C" {
 
 int mnf_affine_half_bwd_split_layout(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                      int64_t* n_split_words, int64_t* n_plain_words) {
-  int hid = 0;
   if (!n_split_words || !n_plain_words || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!has_scale || !has_shift || !mnf::bwd_split_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                   \
-  if (dim == 2 * HH && hid == HD) {                                 \
-    *n_split_words = mnf::BwdSplitShape<HH, HD>::SPLIT_WORDS;       \
-    *n_plain_words = mnf::BwdSplitShape<HH, HD>::PLAIN_WORDS;       \
-    return MNF_OK;                                                  \
-  }
-  MNF_AHF_BWD_SPLIT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::BsRow* r = has_scale && has_shift ? mnf::find_row(dim, n_hidden, hidden) : nullptr;
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  *n_split_words = r->split_words;
+  *n_plain_words = r->plain_words;
+  return MNF_OK;
 }
 
 int mnf_affine_half_bwd_split_index(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                     int32_t* idx_host) {
-  int hid = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!has_scale || !has_shift || !mnf::bwd_split_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD) \
-  if (dim == 2 * HH && hid == HD) return mnf::build_bwd_split_index<HH, HD>(idx_host);
-  MNF_AHF_BWD_SPLIT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::BsRow* r = has_scale && has_shift ? mnf::find_row(dim, n_hidden, hidden) : nullptr;
+  return r ? r->build_index(idx_host) : MNF_ERR_UNSUPPORTED;
 }
 
 int64_t mnf_affine_half_bwd_split_workspace(int64_t rows, int dim, int n_hidden, const int* hidden) {
-  int hid = 0;
-  if (rows < 0 || !mnf::hidden_ok(n_hidden, hidden) || !mnf::bwd_split_uniform3(n_hidden, hidden, hid)) return 0;
-  const int64_t n_tiles = (rows + 15) / 16;
-  int64_t blocks = (n_tiles + mnf::kBsWaves - 1) / mnf::kBsWaves;
-  const int cus = mnf::device_cus(mnf::current_device());
-  if (blocks > cus) blocks = cus;
-#define X(HH, HD) \
-  if (dim == 2 * HH && hid == HD) return blocks * mnf::BwdSplitShape<HH, HD>::RED_FLOATS;
-  MNF_AHF_BWD_SPLIT_SHAPES(X)
-#undef X
-  return 0;
+  const mnf::BsRow* r = rows < 0 || !mnf::hidden_ok(n_hidden, hidden) ? nullptr : mnf::find_row(dim, n_hidden, hidden);
+  return r ? mnf::bwd_split_blocks(rows, mnf::device_cus(mnf::current_device())) * r->red_floats : 0;
 }
 
 int mnf_affine_half_grad_scale(const float* grad_y, const float* grad_ld, int64_t rows, int dim, float* scale_out,
@@ -1050,48 +1043,27 @@ int mnf_affine_half_bwd_split(const float* x, const float* grad_y, const float* 
                               int parity, int inverse, int n_hidden, const int* hidden, const float* grad_scale_dev,
                               int32_t* cold_list, int cold_capacity, float* workspace, int64_t workspace_floats,
                               void* stream) {
-  int hid = 0;
   if (!x || !grad_x || !bwd_image || !index_dev || !cold_list || cold_capacity < 0 || rows < 0 || dim < 2 || (dim & 1) ||
       !mnf::hidden_ok(n_hidden, hidden) || !grad_scale_dev)
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (!mnf::bwd_split_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(grad_x) |
-       reinterpret_cast<uintptr_t>(bwd_image)) & 15)
-    return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                                                                      \
-  if (dim == 2 * HH && hid == HD)                                                                                      \
-    return mnf::launch_bwd_split<HH, HD>(x, grad_y, grad_ld, grad_x, grad_flat, static_cast<const uint32_t*>(bwd_image), \
-                                         index_dev, rows, parity != 0, inverse != 0, grad_scale_dev, cold_list,            \
-                                         cold_capacity, workspace, workspace_floats, (hipStream_t)stream);
-  MNF_AHF_BWD_SPLIT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  return mnf::launch_bwd_split(x, grad_y, grad_ld, grad_x, grad_flat, bwd_image, index_dev, rows, dim, parity, inverse,
+                               n_hidden, hidden, grad_scale_dev, cold_list, cold_capacity, workspace, workspace_floats,
+                               (hipStream_t)stream);
 }
-
 
 int mnf_affine_half_bwd_split_lp(const float* x, const float* lp_grad, float* gy_scratch, float* grad_x,
                               float* grad_flat, const void* bwd_image, const int32_t* index_dev, int64_t rows, int dim,
                               int parity, int inverse, int n_hidden, const int* hidden, const float* grad_scale_dev,
                               int32_t* cold_list, int cold_capacity, float* workspace, int64_t workspace_floats,
                               void* stream) {
-  int hid = 0;
   if (!x || !lp_grad || !gy_scratch || !grad_x || !bwd_image || !index_dev || !cold_list || cold_capacity < 0 || rows < 0 || dim < 2 || (dim & 1) ||
       !mnf::hidden_ok(n_hidden, hidden) || !grad_scale_dev)
     return MNF_ERR_INVALID_ARG;
   if (rows == 0) return MNF_OK;
-  if (!mnf::bwd_split_uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(gy_scratch) | reinterpret_cast<uintptr_t>(grad_x) |
-       reinterpret_cast<uintptr_t>(bwd_image)) & 15)
-    return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                                                                      \
-  if (dim == 2 * HH && hid == HD)                                                                                      \
-    return mnf::launch_bwd_split<HH, HD>(x, nullptr, nullptr, grad_x, grad_flat, static_cast<const uint32_t*>(bwd_image), \
-                                         index_dev, rows, parity != 0, inverse != 0, grad_scale_dev, cold_list,            \
-                                         cold_capacity, workspace, workspace_floats, (hipStream_t)stream, lp_grad, gy_scratch);
-  MNF_AHF_BWD_SPLIT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  return mnf::launch_bwd_split(x, nullptr, nullptr, grad_x, grad_flat, bwd_image, index_dev, rows, dim, parity, inverse,
+                               n_hidden, hidden, grad_scale_dev, cold_list, cold_capacity, workspace, workspace_floats,
+                               (hipStream_t)stream, lp_grad, gy_scratch);
 }
 
 }  // extern "C"

@@ -384,72 +384,63 @@ static void build_index(int32_t* idx, int h, bool has_s = true, bool has_t = tru
         if (16 * m + i < h && has[nn]) b[bt * 16 + i] = net[nn].b_off[3] + 16 * m + i;
 }
 
+// ---------------------------------------------------------------- host: the shape table
+// One row per (H, HID) pair with an instantiated kernel: what the entry points read from the shape, and what they launch.
+using AhfKernel = void (*)(const float*, float*, float*, float*, const float*, int64_t, int, int);
+struct AhfRow {
+  int H, HID, waves;
+  int64_t image_floats;
+  void (*build_index)(int32_t*, int, bool, bool, const int*);
+  AhfKernel kernel[2];  // inverse, forward
+  DeviceMemo resident;  // resident workgroups, by the occupancy of the inverse kernel
+};
 template <int H, int HID>
-static int launch(const float* x, float* y, float* log_det, float* ysq, int accumulate,
-                  const float* image, int64_t rows, int parity, int inverse, hipStream_t stream) {
+static AhfRow make_row() {
   // Measured (tools/ahf_microbench.hip, d = 64, 6 workgroups/CU): 139.5 us without the in-place
   // prefetch, 145 us with it -- six resident waves per SIMD already cover the HBM latency.
   constexpr bool kPrefetch = false;
-  constexpr int kAhfWaves = ahf_waves<H>();
-  const int64_t n_tiles = (rows + 15) / 16;
-  int64_t blocks = (n_tiles + kAhfWaves - 1) / kAhfWaves;
-  // persistent grid: as many workgroups as are resident at once (registers and the LDS image
-  // bound it), each striding over the tiles
-  static DeviceMemo memo;
-  const int resident = memo.get([](int dev) {
-    return resident_by_occupancy(ahf_mfma_kernel<H, HID, true, kPrefetch>, kAhfWaves * 64, dev, 4);
-  });
-  const int cus = device_cus(current_device());
-  blocks = balanced_grid(n_tiles, kAhfWaves, resident, cus);
   // Non-temporal loads/stores are a compile-time experiment switch, off: in the
   // isolated microbench they gain 5 % at d = 64, but inside the 9-layer pass (each layer re-reads
   // what the previous one just wrote) they are neutral at d = 64 and cost 13 % at d = 256.
-  constexpr bool nt = false;  // (rebuild with true for the A/B)
-  constexpr int kNt = 14;  // loads + stores non-temporal (see the ABL list above the kernel)
-  const dim3 grid((unsigned)blocks), block(kAhfWaves * 64);
-  tag_kernel("ahf_mfma_fp32");
-  if constexpr (nt) {
-    if (inverse)
-      hipLaunchKernelGGL((ahf_mfma_kernel<H, HID, true, kPrefetch, kNt>), grid, block, 0, stream, x, y, log_det,
-                         ysq, image, rows, parity, accumulate);
-    else
-      hipLaunchKernelGGL((ahf_mfma_kernel<H, HID, false, kPrefetch, kNt>), grid, block, 0, stream, x, y, log_det,
-                         ysq, image, rows, parity, accumulate);
-  } else {
-    if (inverse)
-      hipLaunchKernelGGL((ahf_mfma_kernel<H, HID, true, kPrefetch>), grid, block, 0, stream, x, y, log_det, ysq,
-                         image, rows, parity, accumulate);
-    else
-      hipLaunchKernelGGL((ahf_mfma_kernel<H, HID, false, kPrefetch>), grid, block, 0, stream, x, y, log_det, ysq,
-                         image, rows, parity, accumulate);
-  }
-  return check_launch();
+  constexpr int kAbl = 0;  // (rebuild with 14 for the A/B: loads + stores non-temporal, see the ABL list above the kernel)
+  return {H, HID, ahf_waves<H>(), AhfShape<H, HID>::IMAGE_FLOATS, build_index<H, HID>,
+          {ahf_mfma_kernel<H, HID, true, kPrefetch, kAbl>, ahf_mfma_kernel<H, HID, false, kPrefetch, kAbl>}, {}};
 }
-
-// (H, HID) pairs with an instantiated kernel
 // reference default hidden width 24 at d = 32..256, plus widths 16 and 32 at the small dims
-#define MNF_AHF_SHAPES(X) X(16, 24) X(32, 24) X(64, 24) X(128, 24) X(16, 16) X(32, 16) X(16, 32) X(32, 32) X(64, 32) X(16, 64) X(32, 64) X(64, 64)
+static AhfRow g_rows[] = {make_row<16, 24>(), make_row<32, 24>(), make_row<64, 24>(), make_row<128, 24>(),
+                          make_row<16, 16>(), make_row<32, 16>(), make_row<16, 32>(),  make_row<32, 32>(),
+                          make_row<64, 32>(), make_row<16, 64>(), make_row<32, 64>(),  make_row<64, 64>()};
 
-// three hidden layers of at most 64 units: hid = the width the kernels run them at (see ahf_padded_hidden)
-static bool uniform_hidden(int n_hidden, const int* hidden, int& hid) {
-  hid = ahf_padded_hidden(n_hidden, hidden);
-  return hid != 0;
+// The row a layer runs at, or null: three hidden layers of at most 64 units at the width ahf_padded_hidden gives, the
+// half h = dim / 2 at its padded width.  h < row->H (a narrow half) has an operand image but no launch here: only the
+// stack kernel runs it, and only at hidden widths 16 / 24 / 32.
+static AhfRow* find_row(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, int& h) {
+  const int hid = ahf_padded_hidden(n_hidden, hidden);
+  if ((!has_scale && !has_shift) || hid == 0) return nullptr;
+  h = dim / 2;
+  const int hp = (dim & 1) ? 0 : ahf_padded_half(h);
+  if (h != hp && hid != 24 && hid != 16 && hid != 32) return nullptr;
+  for (AhfRow& r : g_rows)
+    if (hp == r.H && hid == r.HID) return &r;
+  return nullptr;
 }
 
 int ahf_mfma_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate,
                     const float* image, int64_t rows, int dim, int parity, int inverse, int n_hidden,
                     const int* hidden, int has_scale, int has_shift, hipStream_t stream) {
-  int hid = 0;
-  if ((!has_scale && !has_shift) || !uniform_hidden(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) |
-       reinterpret_cast<uintptr_t>(image)) & 15)
-    return MNF_ERR_UNSUPPORTED;  // float4 accesses need 16-byte aligned bases
-#define X(HH, HD) \
-  if (dim == 2 * HH && hid == HD) \
-    return launch<HH, HD>(x, y, log_det, ysq, accumulate, image, rows, parity != 0, inverse != 0, stream);
-  MNF_AHF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  int h = 0;
+  AhfRow* r = find_row(dim, n_hidden, hidden, has_scale, has_shift, h);
+  if (!r || h != r->H || !aligned16(x, y, image)) return MNF_ERR_UNSUPPORTED;  // float4 accesses need 16-byte aligned bases
+  // persistent grid: as many workgroups as are resident at once (registers and the LDS image
+  // bound it), each striding over the tiles
+  const int resident =
+      r->resident.get([&](int dev) { return resident_by_occupancy(r->kernel[0], r->waves * 64, dev, 4); });
+  const int64_t n_tiles = (rows + 15) / 16;
+  const dim3 grid((unsigned)balanced_grid(n_tiles, r->waves, resident, device_cus(current_device()))), block(r->waves * 64);
+  tag_kernel("ahf_mfma_fp32");
+  hipLaunchKernelGGL(r->kernel[inverse ? 0 : 1], grid, block, 0, stream, x, y, log_det, ysq, image, rows, parity != 0,
+                     accumulate);
+  return check_launch();
 }
 
 }  // namespace mnf
@@ -458,34 +449,20 @@ extern "C" {
 
 int64_t mnf_affine_half_image_floats(int dim, int n_hidden, const int* hidden, int has_scale,
                                      int has_shift) {
-  int hid = 0;
-  if ((!has_scale && !has_shift) || !mnf::hidden_ok(n_hidden, hidden) ||
-      !mnf::uniform_hidden(n_hidden, hidden, hid))
-    return 0;
-  const int h = dim / 2, hp = (dim & 1) ? 0 : mnf::ahf_padded_half(h);
-  if (h != hp && hid != 24 && hid != 16 && hid != 32) return 0;  // a narrow half only has the stack kernel
-#define X(HH, HD) \
-  if (hp == HH && hid == HD) return mnf::AhfShape<HH, HD>::IMAGE_FLOATS;
-  MNF_AHF_SHAPES(X)
-#undef X
-  return 0;
+  int h = 0;
+  if (!mnf::hidden_ok(n_hidden, hidden)) return 0;
+  const mnf::AhfRow* r = mnf::find_row(dim, n_hidden, hidden, has_scale, has_shift, h);
+  return r ? r->image_floats : 0;
 }
 
 int mnf_affine_half_image_index(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                 int32_t* idx_host) {
-  int hid = 0;
+  int h = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if ((!has_scale && !has_shift) || !mnf::uniform_hidden(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int h = dim / 2, hp = (dim & 1) ? 0 : mnf::ahf_padded_half(h);
-  if (h != hp && hid != 24 && hid != 16 && hid != 32) return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                           \
-  if (hp == HH && hid == HD) {              \
-    mnf::build_index<HH, HD>(idx_host, h, has_scale != 0, has_shift != 0, hidden);  \
-    return MNF_OK;                          \
-  }
-  MNF_AHF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::AhfRow* r = mnf::find_row(dim, n_hidden, hidden, has_scale, has_shift, h);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_index(idx_host, h, has_scale != 0, has_shift != 0, hidden);
+  return MNF_OK;
 }
 
 }  // extern "C"

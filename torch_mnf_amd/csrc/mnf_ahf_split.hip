@@ -272,7 +272,7 @@ __device__ __forceinline__ void half_store4(float* p, int col, int h, bool vec, 
   }
 }
 
-// SAMPLE (forward, full tiles: launch_split_stack_sample): the rows are not read but generated, z[r][c] =
+// SAMPLE (forward, full tiles: mnf_affine_half_stack_sample): the rows are not read but generated, z[r][c] =
 // z0_normal(seed, row0 + r, c) (mnf_device.h; mnf_normal_rows writes the same numbers), and y is the only output.  Such a
 // launch has no input rows, no log_det to accumulate into and full tiles, so seed travels in `x` and row0 in `accumulate`
 // (low word) and `h_ragged` (high word); mid, log_det, ysq, log_prob and log_prob_sum are NULL.  A compile-time switch,
@@ -555,173 +555,150 @@ static void build_split_index(int32_t* idx, int h, bool has_s = true, bool has_t
         if (16 * g + i < h && has[nn]) b[bt * 16 + i] = net[nn].b_off[3] + 16 * g + i;
 }
 
+// ---------------------------------------------------------------- host: the shape tables
+// One row per (H, HID) pair with a single-layer split kernel: what the entry points read from the shape, and what
+// ahf_split_launch launches.
+using SplitKernel = void (*)(const float*, float*, float*, float*, const uint32_t*, const float*, int64_t, int, int);
+struct SplitRow {
+  int H, HID;
+  int64_t split_words, plain_words;
+  void (*build_index)(int32_t*, int, bool, bool, const int*);
+  SplitKernel kernel[2];  // inverse, forward
+  DeviceMemo resident;    // resident workgroups, by the occupancy of the inverse kernel
+};
 template <int H, int HID>
-static int launch_split(const float* x, float* y, float* log_det, float* ysq, int accumulate, const uint32_t* simage,
-                        const float* image, int64_t rows, int parity, int inverse, hipStream_t stream) {
-  static DeviceMemo memo;
-  const int resident = memo.get([](int dev) {
-    return resident_by_occupancy(ahf_split_kernel<H, HID, true>, kSplitWaves * 64, dev, 1);
-  });
-  const int cus = device_cus(current_device());
-  const int64_t n_tiles = (rows + 15) / 16;
-  const dim3 grid((unsigned)balanced_grid(n_tiles, kSplitWaves, resident, cus)), block(kSplitWaves * 64);
-  tag_kernel("ahf_split");
-  if (inverse)
-    hipLaunchKernelGGL((ahf_split_kernel<H, HID, true>), grid, block, 0, stream, x, y, log_det, ysq, simage, image,
-                       rows, parity, accumulate);
-  else
-    hipLaunchKernelGGL((ahf_split_kernel<H, HID, false>), grid, block, 0, stream, x, y, log_det, ysq, simage, image,
-                       rows, parity, accumulate);
-  return check_launch();
+static SplitRow make_split_row() {
+  using S = SplitShape<H, HID>;
+  return {H, HID, S::SPLIT_WORDS, S::PLAIN_WORDS, build_split_index<H, HID>,
+          {ahf_split_kernel<H, HID, true>, ahf_split_kernel<H, HID, false>}, {}};
 }
+static SplitRow g_split_rows[] = {make_split_row<16, 24>(), make_split_row<32, 24>(),  make_split_row<16, 16>(),
+                                  make_split_row<32, 16>(), make_split_row<64, 24>(),  make_split_row<128, 24>(),
+                                  make_split_row<16, 32>(), make_split_row<32, 32>(),  make_split_row<64, 32>(),
+                                  make_split_row<16, 64>(), make_split_row<32, 64>(),  make_split_row<64, 64>()};
 
-template <int H, int HID, bool RAG>
-static int launch_split_stack(const float* x, float* y, float* mid, float* log_det, float* ysq, int accumulate,
-                              const uint32_t* simages, const float* images, uint32_t parity_bits, int n_layers,
-                              int64_t rows, int inverse, float* log_prob, double* log_prob_sum, int h, int vec_ok,
-                              hipStream_t stream) {
-  constexpr int kStackWaves = stack_waves<H>(), kStackTiles = stack_tiles<H>();
+// ... and the rows of the stack kernel: one per pair with its four variants by (full tiles / narrow half) and direction,
+// then one per pair for the sample launch, which runs the SAMPLE instantiation on the same grid.
+using StackKernel = void (*)(const float*, float*, float*, float*, float*, const uint32_t*, const float*, uint32_t, int,
+                             int64_t, int, float*, double*, int, int);
+struct StackRow {
+  int H, HID;
+  bool sample;
+  int waves, group_rows;
+  size_t lds_bytes;          // the dynamic part of the two images (see the kernel)
+  int per_cu;                // workgroups a CU holds
+  StackKernel kernel[2][2];  // [ragged][inverse, forward]; null: no such kernel
+  DeviceMemo resident[2];    // [ragged], per device: 0 = not set up yet, -1 = the dynamic-LDS attribute could not be set,
+                             // else the number of resident workgroups
+};
+template <int H, int HID, bool SAMPLE = false>
+static StackRow make_stack_row() {
   constexpr size_t image_bytes = 2 * SplitShape<H, HID>::IMAGE_WORDS * sizeof(uint32_t);
-  constexpr size_t lds_bytes = image_bytes <= 64 * 1024 ? 0 : image_bytes;  // dynamic part (see the kernel)
-  // per device (the dynamic-LDS attribute is a per-device setting of the function; a process may drive several GPUs):
-  // 0 = not set up yet, -1 = the attribute could not be set, else the number of resident workgroups
-  static DeviceMemo memo;
-  const int resident = memo.get([](int dev) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_split_stack_kernel<H, HID, true, RAG>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_split_stack_kernel<H, HID, false, RAG>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-      return -1;
-    // two waves per SIMD by registers (launch bounds), i.e. 8 waves per CU; the double-buffered image fits twice
-    // for d <= 64 (the occupancy query under-reports kernels with dynamic LDS, so this is computed here)
-    int per_cu = 4 * stack_waves_per_simd<H>() / kStackWaves;
-    while (per_cu > 1 && per_cu * image_bytes > 160 * 1024) --per_cu;
-    return per_cu * device_cus(dev);
-  });
-  if (resident <= 0) return MNF_ERR_UNSUPPORTED;
-  constexpr int GROUP_ROWS = 16 * kStackTiles * kStackWaves;
-  const int64_t n_groups = (rows + GROUP_ROWS - 1) / GROUP_ROWS;
-  const dim3 grid((unsigned)(n_groups < resident ? n_groups : resident)), block(kStackWaves * 64);
-  tag_kernel("ahf_split_stack");
-  if (inverse)
-    hipLaunchKernelGGL((ahf_split_stack_kernel<H, HID, true, RAG>), grid, block, lds_bytes, stream, x, y, mid, log_det,
-                       ysq, simages, images, parity_bits, n_layers, rows, accumulate, log_prob, log_prob_sum, h, vec_ok);
+  constexpr size_t lds_bytes = image_bytes <= 64 * 1024 ? 0 : image_bytes;
+  constexpr int waves = stack_waves<H>(), group_rows = 16 * stack_tiles<H>() * waves;
+  // two waves per SIMD by registers (launch bounds), i.e. 8 waves per CU; the double-buffered image fits twice
+  // for d <= 64 (the occupancy query under-reports kernels with dynamic LDS, so this is computed here)
+  int per_cu = 4 * stack_waves_per_simd<H>() / waves;
+  while (per_cu > 1 && per_cu * image_bytes > 160 * 1024) --per_cu;
+  if constexpr (SAMPLE)
+    return {H, HID, true, waves, group_rows, lds_bytes, per_cu,
+            {{nullptr, ahf_split_stack_kernel<H, HID, false, false, true>}, {}}, {}};
   else
-    hipLaunchKernelGGL((ahf_split_stack_kernel<H, HID, false, RAG>), grid, block, lds_bytes, stream, x, y, mid, log_det,
-                       ysq, simages, images, parity_bits, n_layers, rows, accumulate, log_prob, log_prob_sum, h, vec_ok);
-  return check_launch();
+    return {H, HID, false, waves, group_rows, lds_bytes, per_cu,
+            {{ahf_split_stack_kernel<H, HID, true, false>, ahf_split_stack_kernel<H, HID, false, false>},
+             {ahf_split_stack_kernel<H, HID, true, true>, ahf_split_stack_kernel<H, HID, false, true>}}, {}};
 }
+// (hidden width 64 has no stack kernel; 32 at d <= 64 spills at two tiles per wave and gains nothing over nine
+// single-layer launches: there it only serves narrow halves, see find_stack_row)
+static StackRow g_stack_rows[] = {
+    make_stack_row<16, 24>(),       make_stack_row<32, 24>(),       make_stack_row<16, 16>(),
+    make_stack_row<32, 16>(),       make_stack_row<64, 24>(),       make_stack_row<128, 24>(),
+    make_stack_row<16, 32>(),       make_stack_row<32, 32>(),       make_stack_row<64, 32>(),
+    make_stack_row<16, 24, true>(), make_stack_row<32, 24, true>(), make_stack_row<16, 16, true>(),
+    make_stack_row<32, 16, true>(), make_stack_row<64, 24, true>(), make_stack_row<128, 24, true>(),
+    make_stack_row<16, 32, true>(), make_stack_row<32, 32, true>(), make_stack_row<64, 32, true>()};
 
-// (H, HID) pairs with a split kernel, and those of the stack kernel (hidden width 32 at d <= 64 spills at two tiles
-// per wave and gains nothing over nine single-layer launches: there it only serves narrow halves, see below)
-#define MNF_AHF_SPLIT_SHAPES(X) X(16, 24) X(32, 24) X(16, 16) X(32, 16) X(64, 24) X(128, 24) X(16, 32) X(32, 32) X(64, 32) X(16, 64) X(32, 64) X(64, 64)
-#define MNF_AHF_SPLIT_STACK_SHAPES(X) X(16, 24) X(32, 24) X(16, 16) X(32, 16) X(64, 24) X(128, 24) X(16, 32) X(32, 32) X(64, 32)
-
-// three hidden layers of at most 64 units: hid = the width the kernels run them at (see ahf_padded_hidden)
-static bool uniform3(int n_hidden, const int* hidden, int& hid) {
-  hid = ahf_padded_hidden(n_hidden, hidden);
-  return hid != 0;
+// the stack table's row of a tile half and hidden width, or null
+static StackRow* stack_row(int hp, int hid, bool sample = false) {
+  for (StackRow& r : g_stack_rows)
+    if (hp == r.H && hid == r.HID && sample == r.sample) return &r;
+  return nullptr;
 }
-
-static bool aligned16(const void* a, const void* b, const void* c, const void* d) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+// The stack kernel's row for layers of `dim` columns run at hidden width `hid` (ahf_padded_hidden), or null.  h = dim / 2;
+// h < row->H: a narrow half, which only the ragged variant runs.
+static StackRow* find_stack_row(int dim, int hid, int n_layers, int& h, bool sample = false) {
+  h = dim / 2;
+  const int hp = (dim & 1) ? 0 : ahf_padded_half(h);
+  if (hid == 32 && h == hp && hp <= 32 && n_layers > 1) return nullptr;  // measured: no faster than layer by layer
+  return stack_row(hp, hid, sample);
+}
+// The row of a layer's split image, or null.  Full tiles: every split shape; a narrow half: the shapes of the stack kernel
+// (its only kernel).
+static SplitRow* find_split_row(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift, int& h) {
+  const int hid = ahf_padded_hidden(n_hidden, hidden);  // three hidden layers of at most 64 units
+  if ((!has_scale && !has_shift) || hid == 0) return nullptr;
+  h = dim / 2;
+  const int hp = (dim & 1) ? 0 : ahf_padded_half(h);
+  if (h != hp && !stack_row(hp, hid)) return nullptr;
+  for (SplitRow& r : g_split_rows)
+    if (hp == r.H && hid == r.HID) return &r;
+  return nullptr;
 }
 
 int ahf_split_launch(const float* x, float* y, float* log_det, float* ysq, int accumulate, const void* split_image,
                      const float* image, int64_t rows, int dim, int parity, int inverse, int n_hidden,
                      const int* hidden, int has_scale, int has_shift, hipStream_t stream) {
-  int hid = 0;
-  if (!split_image || !image || (!has_scale && !has_shift) || !uniform3(n_hidden, hidden, hid))
-    return MNF_ERR_UNSUPPORTED;
-  if (!aligned16(x, y, split_image, image)) return MNF_ERR_UNSUPPORTED;
-#define X(HH, HD)                                                                                            \
-  if (dim == 2 * HH && hid == HD)                                                                            \
-    return launch_split<HH, HD>(x, y, log_det, ysq, accumulate, static_cast<const uint32_t*>(split_image), image, \
-                                rows, parity != 0, inverse != 0, stream);
-  MNF_AHF_SPLIT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  int h = 0;
+  SplitRow* r = split_image && image ? find_split_row(dim, n_hidden, hidden, has_scale, has_shift, h) : nullptr;
+  if (!r || h != r->H || !aligned16(x, y, split_image, image)) return MNF_ERR_UNSUPPORTED;
+  const int resident =
+      r->resident.get([&](int dev) { return resident_by_occupancy(r->kernel[0], kSplitWaves * 64, dev, 1); });
+  const int64_t n_tiles = (rows + 15) / 16;
+  const dim3 grid((unsigned)balanced_grid(n_tiles, kSplitWaves, resident, device_cus(current_device()))),
+      block(kSplitWaves * 64);
+  tag_kernel("ahf_split");
+  hipLaunchKernelGGL(r->kernel[inverse ? 0 : 1], grid, block, 0, stream, x, y, log_det, ysq,
+                     static_cast<const uint32_t*>(split_image), image, rows, parity != 0, accumulate);
+  return check_launch();
+}
+
+// one launch of a row's kernel, with the kernel's own argument list
+static int launch_split_stack(StackRow& r, bool ragged, int inverse, const float* x, float* y, float* mid, float* log_det,
+                              float* ysq, const void* split_images, const float* images, uint32_t parity_bits,
+                              int n_layers, int64_t rows, int accumulate, float* log_prob, double* log_prob_sum, int h,
+                              int vec_ok, hipStream_t stream) {
+  const int resident = dynamic_lds_memo(r.resident[ragged], r.lds_bytes, r.kernel[ragged], 2,
+                                        [&](int dev) { return r.per_cu * device_cus(dev); });
+  if (resident <= 0) return MNF_ERR_UNSUPPORTED;
+  const int64_t n_groups = (rows + r.group_rows - 1) / r.group_rows;
+  const dim3 grid((unsigned)(n_groups < resident ? n_groups : resident)), block(r.waves * 64);
+  tag_kernel(r.sample ? "ahf_split_stack_sample" : "ahf_split_stack");
+  hipLaunchKernelGGL(r.kernel[ragged][inverse ? 0 : 1], grid, block, r.lds_bytes, stream, x, y, mid, log_det, ysq,
+                     static_cast<const uint32_t*>(split_images), images, parity_bits, n_layers, rows, accumulate,
+                     log_prob, log_prob_sum, h, vec_ok);
+  return check_launch();
 }
 
 int ahf_split_stack_launch(const float* x, float* y, float* mid, float* log_det, float* ysq, int accumulate,
                            const void* split_images, const float* images, uint32_t parity_bits, int n_layers,
                            int64_t rows, int dim, int inverse, int hid, float* log_prob, double* log_prob_sum,
                            hipStream_t stream) {
-  if (!split_images || !images || (dim & 1) || !aligned16(split_images, images, nullptr, nullptr))
-    return MNF_ERR_UNSUPPORTED;
-  const int h = dim / 2, hp = ahf_padded_half(h);
-  const bool rows_aligned = aligned16(x, y, mid, nullptr);
-  if (h == hp && !rows_aligned) return MNF_ERR_UNSUPPORTED;
-  const int vec_ok = rows_aligned && (h & 3) == 0;
-  if (hid == 32 && h == hp && hp <= 32 && n_layers > 1) return MNF_ERR_UNSUPPORTED;  // measured: no faster than layer by layer
-  const uint32_t* simages = static_cast<const uint32_t*>(split_images);
-#define X(HH, HD)                                                                                                    \
-  if (hp == HH && hid == HD)                                                                                         \
-    return h == HH ? launch_split_stack<HH, HD, false>(x, y, mid, log_det, ysq, accumulate, simages, images,         \
-                                                       parity_bits, n_layers, rows, inverse != 0, log_prob,         \
-                                                       log_prob_sum, h, vec_ok, stream)                              \
-                   : launch_split_stack<HH, HD, true>(x, y, mid, log_det, ysq, accumulate, simages, images,          \
-                                                      parity_bits, n_layers, rows, inverse != 0, log_prob,          \
-                                                      log_prob_sum, h, vec_ok, stream);
-  MNF_AHF_SPLIT_STACK_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  int h = 0;
+  StackRow* r = split_images && images ? find_stack_row(dim, hid, n_layers, h) : nullptr;
+  if (!r || !aligned16(split_images, images)) return MNF_ERR_UNSUPPORTED;
+  const bool rows_aligned = aligned16(x, y, mid);
+  if (h == r->H && !rows_aligned) return MNF_ERR_UNSUPPORTED;
+  return launch_split_stack(*r, h != r->H, inverse, x, y, mid, log_det, ysq, split_images,
+                            images, parity_bits, n_layers, rows, accumulate, log_prob, log_prob_sum, h,
+                            rows_aligned && (h & 3) == 0, stream);
 }
 
 // The shapes with a sample launch: the stack kernel's full-tile forward instantiations (a narrow half runs on the ragged
 // variant, which has no noise source), under the stack launcher's own rule for hidden width 32.
-static bool stack_sample_shape(int dim, int hid, int n_layers) {
-  if (dim < 2 || (dim & 1) || n_layers < 1 || n_layers > 32) return false;
-  const int h = dim / 2;
-  if (h != ahf_padded_half(h)) return false;
-  if (hid == 32 && h <= 32 && n_layers > 1) return false;
-#define X(HH, HD) \
-  if (h == HH && hid == HD) return true;
-  MNF_AHF_SPLIT_STACK_SHAPES(X)
-#undef X
-  return false;
-}
-
-// the SAMPLE instantiation on launch_split_stack's grid: seed rides in x, row0 in accumulate | h << 32 (see the kernel)
-template <int H, int HID>
-static int launch_split_stack_sample(uint64_t seed, int64_t row0, float* y, const uint32_t* simages, const float* images,
-                                     uint32_t parity_bits, int n_layers, int64_t rows, hipStream_t stream) {
-  constexpr int kStackWaves = stack_waves<H>(), kStackTiles = stack_tiles<H>();
-  constexpr size_t image_bytes = 2 * SplitShape<H, HID>::IMAGE_WORDS * sizeof(uint32_t);
-  constexpr size_t lds_bytes = image_bytes <= 64 * 1024 ? 0 : image_bytes;
-  static DeviceMemo memo;
-  const int resident = memo.get([](int dev) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ahf_split_stack_kernel<H, HID, false, false, true>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess)
-      return -1;
-    int per_cu = 4 * stack_waves_per_simd<H>() / kStackWaves;  // (as launch_split_stack)
-    while (per_cu > 1 && per_cu * image_bytes > 160 * 1024) --per_cu;
-    return per_cu * device_cus(dev);
-  });
-  if (resident <= 0) return MNF_ERR_UNSUPPORTED;
-  constexpr int GROUP_ROWS = 16 * kStackTiles * kStackWaves;
-  const int64_t n_groups = (rows + GROUP_ROWS - 1) / GROUP_ROWS;
-  const dim3 grid((unsigned)(n_groups < resident ? n_groups : resident)), block(kStackWaves * 64);
-  tag_kernel("ahf_split_stack_sample");
-  hipLaunchKernelGGL((ahf_split_stack_kernel<H, HID, false, false, true>), grid, block, lds_bytes, stream,
-                     reinterpret_cast<const float*>(seed), y, (float*)nullptr, (float*)nullptr, (float*)nullptr, simages,
-                     images, parity_bits, n_layers, rows, (int)(uint32_t)row0, (float*)nullptr, (double*)nullptr,
-                     (int)(uint32_t)((uint64_t)row0 >> 32), 1);
-  return check_launch();
-}
-
-static int ahf_split_stack_sample_launch(uint64_t seed, int64_t row0, float* y, const void* split_images,
-                                         const float* images, uint32_t parity_bits, int n_layers, int64_t rows, int dim,
-                                         int hid, hipStream_t stream) {
-  if (!stack_sample_shape(dim, hid, n_layers) || !aligned16(y, split_images, images, nullptr)) return MNF_ERR_UNSUPPORTED;
-  const uint32_t* simages = static_cast<const uint32_t*>(split_images);
-#define X(HH, HD)                  \
-  if (dim == 2 * HH && hid == HD)  \
-    return launch_split_stack_sample<HH, HD>(seed, row0, y, simages, images, parity_bits, n_layers, rows, stream);
-  MNF_AHF_SPLIT_STACK_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+static StackRow* find_sample_row(int dim, int hid, int n_layers) {
+  int h = 0;
+  StackRow* r = n_layers < 1 || n_layers > 32 ? nullptr : find_stack_row(dim, hid, n_layers, h, true);
+  return r && h == r->H ? r : nullptr;
 }
 
 }  // namespace mnf
@@ -730,7 +707,7 @@ extern "C" {
 
 int mnf_affine_half_stack_sample_supported(int dim, int n_hidden, const int* hidden_host, int n_layers) {
   return mnf::hidden_ok(n_hidden, hidden_host) &&
-         mnf::stack_sample_shape(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers);
+         mnf::find_sample_row(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers) != nullptr;
 }
 
 int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const float* images, const void* split_images,
@@ -742,49 +719,33 @@ int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const fl
   if (rows == 0) return MNF_OK;
   uint32_t bits = 0;
   for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
-  return mnf::ahf_split_stack_sample_launch(seed, row0, y, split_images, images, bits, n_layers, rows, dim,
-                                            mnf::ahf_padded_hidden(n_hidden, hidden_host), (hipStream_t)stream);
+  mnf::StackRow* r = mnf::find_sample_row(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers);
+  if (!r || !mnf::aligned16(y, split_images, images)) return MNF_ERR_UNSUPPORTED;
+  // the SAMPLE instantiation on the stack launch's grid: seed rides in x, row0 in accumulate | h << 32 (see the kernel)
+  return mnf::launch_split_stack(*r, false, 0, reinterpret_cast<const float*>(seed), y, nullptr, nullptr,
+                                 nullptr, split_images, images, bits, n_layers, rows, (int)(uint32_t)row0, nullptr, nullptr,
+                                 (int)(uint32_t)((uint64_t)row0 >> 32), 1, (hipStream_t)stream);
 }
 
 int mnf_affine_half_split_layout(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                  int64_t* n_split_words, int64_t* n_plain_words) {
-  int hid = 0;
+  int h = 0;
   if (!n_split_words || !n_plain_words || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if ((!has_scale && !has_shift) || !mnf::uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int h = dim / 2, hp = (dim & 1) ? 0 : mnf::ahf_padded_half(h);
-#define X(HH, HD)                                            \
-  if (hp == HH && hid == HD) {                               \
-    *n_split_words = mnf::SplitShape<HH, HD>::SPLIT_WORDS;   \
-    *n_plain_words = mnf::SplitShape<HH, HD>::PLAIN_WORDS;   \
-    return MNF_OK;                                           \
-  }
-  if (h == hp) {  // full tiles: every split shape; a ragged half: the shapes of the stack kernel (its only kernel)
-    MNF_AHF_SPLIT_SHAPES(X)
-  } else {
-    MNF_AHF_SPLIT_STACK_SHAPES(X)
-  }
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::SplitRow* r = mnf::find_split_row(dim, n_hidden, hidden, has_scale, has_shift, h);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  *n_split_words = r->split_words;
+  *n_plain_words = r->plain_words;
+  return MNF_OK;
 }
 
 int mnf_affine_half_split_index(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,
                                 int32_t* idx_host) {
-  int hid = 0;
+  int h = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if ((!has_scale && !has_shift) || !mnf::uniform3(n_hidden, hidden, hid)) return MNF_ERR_UNSUPPORTED;
-  const int h = dim / 2, hp = (dim & 1) ? 0 : mnf::ahf_padded_half(h);
-#define X(HH, HD)                                 \
-  if (hp == HH && hid == HD) {                    \
-    mnf::build_split_index<HH, HD>(idx_host, h, has_scale != 0, has_shift != 0, hidden);  \
-    return MNF_OK;                                \
-  }
-  if (h == hp) {
-    MNF_AHF_SPLIT_SHAPES(X)
-  } else {
-    MNF_AHF_SPLIT_STACK_SHAPES(X)
-  }
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::SplitRow* r = mnf::find_split_row(dim, n_hidden, hidden, has_scale, has_shift, h);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_index(idx_host, h, has_scale != 0, has_shift != 0, hidden);
+  return MNF_OK;
 }
 
 }  // extern "C"

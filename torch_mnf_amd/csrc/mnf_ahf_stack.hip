@@ -169,8 +169,7 @@ int mnf_affine_half_stack(const float* x, float* y, float* intermediates, float*
     if (rc != MNF_ERR_UNSUPPORTED) return rc;
   }
   if (log_prob || log_prob_sum) return MNF_ERR_UNSUPPORTED;  // only the split kernel has the fused log-prob epilogue
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(images) |
-       reinterpret_cast<uintptr_t>(intermediates)) & 15)
+  if (!mnf::aligned16(x, y, images, intermediates))
     return MNF_ERR_UNSUPPORTED;  // 16-byte row accesses (the split launcher has its own check: narrow halves need none)
 #define X(HH, HD) \
   if (dim == 2 * HH && hid == HD) \

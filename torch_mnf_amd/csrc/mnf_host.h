@@ -77,6 +77,23 @@ inline int resident_by_occupancy(K kernel, int threads, int dev, int fallback) {
     per_cu = fallback;
   return per_cu * device_cus(dev);
 }
+// `bytes` of dynamic LDS allowed for each of kernels[0 .. n) (null entries: variants a shape does not have), set once per
+// device through the call site's `memo`: value(dev) (> 0) from then on, -1 if the device refuses one of them
+template <typename K, typename F>
+inline int dynamic_lds_memo(DeviceMemo& memo, size_t bytes, const K* kernels, int n, F value) {
+  return memo.get([&](int dev) {
+    for (int i = 0; i < n; ++i)
+      if (kernels[i] && hipFuncSetAttribute(reinterpret_cast<const void*>(kernels[i]),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
+        return -1;
+    return (int)value(dev);
+  });
+}
+// every pointer 16-byte aligned (a null one is): the kernels' dwordx4 row accesses
+template <typename... P>
+inline bool aligned16(const P*... p) {
+  return (((reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
+}
 
 // Persistent-grid sizing: among grids of whole workgroups-per-CU steps between resident/2 and
 // resident, pick the one whose static tile striding wastes the fewest wave-rounds

@@ -788,56 +788,63 @@ static void build_tables(int hr, const int* w, int32_t* idx, int32_t* flush) {
   }
 }
 
+// ---------------------------------------------------------------- host: the shape table
+struct NtRow {
+  int H, NH, K, waves;
+  int64_t split_words, plain_words;
+  size_t lds_bytes;
+  void (*build_tables)(int, const int*, int32_t*, int32_t*);
+  NtKernel kernel[2][2];  // [inverse][stage]
+  DeviceMemo attr[2][2];  // the kernel's dynamic-LDS attribute is set on the device: 1, -1 if it cannot be
+};
 template <int H, int NH, int K>
-static int launch_tile(const NtArgs& a, int inverse, hipStream_t stream) {
+static NtRow make_row() {
   using Sh = NtShape<H, NH, K>;
+  return {H, NH, K, Sh::WAVES, Sh::SPLIT_WORDS, Sh::PLAIN_WORDS, (size_t)Sh::LDS_WORDS * 4, build_tables<H, NH, K>,
+          {{NtKernelOf<H, NH, K, false, 0>::get(), NtKernelOf<H, NH, K, false, 1>::get()},
+           {NtKernelOf<H, NH, K, true, 0>::get(), NtKernelOf<H, NH, K, true, 1>::get()}}, {}};
+}
+static NtRow g_rows[] = {make_row<16, 8, 8>(),  make_row<16, 8, 5>(),  make_row<16, 16, 8>(), make_row<16, 16, 5>(),
+                         make_row<32, 8, 8>(),  make_row<32, 8, 5>(),  make_row<32, 16, 8>(), make_row<32, 16, 5>(),
+                         make_row<16, 8, 10>(), make_row<16, 16, 10>()};
+
+// The row of a layer, or null: three hidden layers of at most 16 units (run at 8 or 16), the half hr = dim / 2 of whole
+// float4 groups (run at 16 or 32).
+static NtRow* find_row(int dim, int K, int n_hidden, const int* hidden) {
+  if (n_hidden != 3 || !hidden || dim < 8 || (dim & 7) || dim > 64) return nullptr;
+  int mx = 0;
+  for (int i = 0; i < 3; ++i) {
+    if (hidden[i] < 1) return nullptr;
+    mx = hidden[i] > mx ? hidden[i] : mx;
+  }
+  const int hp = dim / 2 <= 16 ? 16 : 32, nh = mx <= 8 ? 8 : (mx <= 16 ? 16 : 0);
+  for (NtRow& r : g_rows)
+    if (hp == r.H && nh == r.NH && K == r.K) return &r;
+  return nullptr;
+}
+// the parameter count of a layer that has a row
+static int64_t tile_params(int dim, int K, const int* hidden) {
+  int sizes[5] = {dim / 2, hidden[0], hidden[1], hidden[2], (3 * K - 1) * (dim / 2)};
+  NetDesc nd;
+  return 2 * fill_net(nd, 5, sizes, 0);
+}
+
+static int launch_tile(NtRow& r, const NtArgs& a, int inverse, hipStream_t stream) {
   const int64_t n_tiles = (a.rows + 15) / 16;
-  int64_t blocks = (n_tiles + Sh::WAVES - 1) / Sh::WAVES;
+  int64_t blocks = (n_tiles + r.waves - 1) / r.waves;
   const int cus = device_cus(current_device());
   if (blocks > cus) blocks = cus;  // one persistent workgroup per CU: the sums take the register file
-  const size_t lds_bytes = (size_t)Sh::LDS_WORDS * 4;
-  static DeviceMemo attr[4];
   tag_kernel("nsf_bwd_tile");
   for (int st = 0; st < 2; ++st) {
-    const NtKernel kernel = inverse ? (st ? NtKernelOf<H, NH, K, true, 1>::get() : NtKernelOf<H, NH, K, true, 0>::get())
-                                    : (st ? NtKernelOf<H, NH, K, false, 1>::get() : NtKernelOf<H, NH, K, false, 0>::get());
-    const int ok = attr[2 * (inverse ? 1 : 0) + st].get([&](int) {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds_bytes) == hipSuccess ? 1 : -1;
-    });
-    if (ok < 0) return MNF_ERR_LAUNCH;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(Sh::WAVES * 64), lds_bytes, stream, a);
+    const NtKernel* kernel = &r.kernel[inverse ? 1 : 0][st];
+    if (dynamic_lds_memo(r.attr[inverse ? 1 : 0][st], r.lds_bytes, kernel, 1, [](int) { return 1; }) < 0)
+      return MNF_ERR_LAUNCH;
+    hipLaunchKernelGGL(*kernel, dim3((unsigned)blocks), dim3(r.waves * 64), r.lds_bytes, stream, a);
     if (int rc = check_launch()) return rc;
   }
   hipLaunchKernelGGL(nsf_tile_reduce_kernel, dim3((unsigned)((a.n_params + 31) / 32)), dim3(256), 0, stream, a.partials,
                      (int)blocks, a.n_params, a.grad_flat, a.scale_dev, a.cold);
   return check_launch();
-}
-
-// (H, NH, K) triples with an instantiated kernel
-#define MNF_NT_SHAPES(X) X(16, 8, 8) X(16, 8, 5) X(16, 16, 8) X(16, 16, 5) X(32, 8, 8) X(32, 8, 5) X(32, 16, 8) X(32, 16, 5) X(16, 8, 10) X(16, 16, 10)
-
-struct TileShape {
-  int H, NH, K, hr;
-  int w[3];
-};
-static bool tile_shape(int dim, int K, int n_hidden, const int* hidden, TileShape& ts) {
-  if (n_hidden != 3 || !hidden || dim < 8 || (dim & 7) || dim > 64) return false;
-  int mx = 0;
-  for (int i = 0; i < 3; ++i) {
-    if (hidden[i] < 1) return false;
-    ts.w[i] = hidden[i];
-    mx = hidden[i] > mx ? hidden[i] : mx;
-  }
-  ts.hr = dim / 2;
-  ts.H = ts.hr <= 16 ? 16 : 32;
-  ts.NH = mx <= 8 ? 8 : (mx <= 16 ? 16 : 0);
-  ts.K = K;
-#define X(HH, NHH, KK) \
-  if (ts.H == HH && ts.NH == NHH && K == KK) return true;
-  MNF_NT_SHAPES(X)
-#undef X
-  return false;
 }
 
 }  // namespace
@@ -846,47 +853,31 @@ static bool tile_shape(int dim, int K, int n_hidden, const int* hidden, TileShap
 extern "C" {
 
 int mnf_nsf_cl_bwd_tile_supported(int dim, int K, int n_hidden, const int* hidden) {
-  mnf::TileShape ts;
-  return mnf::tile_shape(dim, K, n_hidden, hidden, ts) ? 1 : 0;
+  return mnf::find_row(dim, K, n_hidden, hidden) ? 1 : 0;
 }
 
 int mnf_nsf_cl_bwd_tile_layout(int dim, int K, int n_hidden, const int* hidden, int64_t* n_split_words,
                                int64_t* n_plain_words, int64_t* n_params) {
-  mnf::TileShape ts;
   if (!n_split_words || !n_plain_words || !n_params || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!mnf::tile_shape(dim, K, n_hidden, hidden, ts)) return MNF_ERR_UNSUPPORTED;
-  int sizes[5] = {ts.hr, ts.w[0], ts.w[1], ts.w[2], (3 * K - 1) * ts.hr};
-  mnf::NetDesc nd;
-  *n_params = 2 * mnf::fill_net(nd, 5, sizes, 0);
-#define X(HH, NHH, KK)                                             \
-  if (ts.H == HH && ts.NH == NHH && K == KK) {                     \
-    *n_split_words = mnf::NtShape<HH, NHH, KK>::SPLIT_WORDS;       \
-    *n_plain_words = mnf::NtShape<HH, NHH, KK>::PLAIN_WORDS;       \
-    return MNF_OK;                                                 \
-  }
-  MNF_NT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::NtRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  *n_params = mnf::tile_params(dim, K, hidden);
+  *n_split_words = r->split_words;
+  *n_plain_words = r->plain_words;
+  return MNF_OK;
 }
 
 int mnf_nsf_cl_bwd_tile_index(int dim, int K, int n_hidden, const int* hidden, int32_t* idx_host, int32_t* flush_host) {
-  mnf::TileShape ts;
   if (!idx_host || !flush_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!mnf::tile_shape(dim, K, n_hidden, hidden, ts)) return MNF_ERR_UNSUPPORTED;
-#define X(HH, NHH, KK)                                                     \
-  if (ts.H == HH && ts.NH == NHH && K == KK) {                             \
-    mnf::build_tables<HH, NHH, KK>(ts.hr, ts.w, idx_host, flush_host);     \
-    return MNF_OK;                                                         \
-  }
-  MNF_NT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::NtRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_tables(dim / 2, hidden, idx_host, flush_host);
+  return MNF_OK;
 }
 
 int64_t mnf_nsf_cl_bwd_tile_workspace(int64_t rows, int dim, int K, int n_hidden, const int* hidden) {
-  int64_t sw = 0, pw = 0, np = 0;
-  if (rows < 0 || mnf_nsf_cl_bwd_tile_layout(dim, K, n_hidden, hidden, &sw, &pw, &np) != MNF_OK) return 0;
-  return (int64_t)mnf::device_cus(mnf::current_device()) * np;
+  if (rows < 0 || !mnf::hidden_ok(n_hidden, hidden) || !mnf::find_row(dim, K, n_hidden, hidden)) return 0;
+  return (int64_t)mnf::device_cus(mnf::current_device()) * mnf::tile_params(dim, K, hidden);
 }
 
 int mnf_nsf_cl_bwd_tile(const float* x, const float* y, const float* grad_y, const float* grad_ld, float* grad_x, float* grad_flat,
@@ -896,12 +887,10 @@ int mnf_nsf_cl_bwd_tile(const float* x, const float* y, const float* grad_y, con
   if (!x || !y || !grad_x || !grad_flat || !image || !flush || !scale_dev || !cold || !workspace || rows < 0 || dim < 2 ||
       (dim & 1) || K < 2 || !(tail_bound > 0.f) || !mnf::hidden_ok(n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
-  mnf::TileShape ts;
-  if (!mnf::tile_shape(dim, K, n_hidden, hidden, ts)) return MNF_ERR_UNSUPPORTED;
+  mnf::NtRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
   if (rows * dim >= (1ll << 31)) return MNF_ERR_UNSUPPORTED;  // (32-bit element offsets: the caller's generic kernel)
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(grad_y) |
-       reinterpret_cast<uintptr_t>(grad_x) | reinterpret_cast<uintptr_t>(image)) & 15)
-    return MNF_ERR_UNSUPPORTED;
+  if (!mnf::aligned16(x, y, grad_y, grad_x, image)) return MNF_ERR_UNSUPPORTED;
   if (rows == 0) return MNF_OK;
   if (cold_capacity < (rows + 15) / 16 || workspace_floats < mnf_nsf_cl_bwd_tile_workspace(rows, dim, K, n_hidden, hidden))
     return MNF_ERR_INVALID_ARG;
@@ -909,15 +898,9 @@ int mnf_nsf_cl_bwd_tile(const float* x, const float* y, const float* grad_y, con
   memset(&a, 0, sizeof(a));
   a.x = x; a.y = y; a.grad_y = grad_y; a.grad_ld = grad_ld; a.grad_x = grad_x; a.grad_flat = grad_flat;
   a.image = static_cast<const uint32_t*>(image); a.flush = flush; a.partials = workspace; a.scale_dev = scale_dev;
-  a.cold = cold; a.cold_capacity = cold_capacity; a.rows = rows; a.T = tail_bound; a.hr = ts.hr;
-  int sizes[5] = {ts.hr, ts.w[0], ts.w[1], ts.w[2], (3 * K - 1) * ts.hr};
-  mnf::NetDesc nd;
-  a.n_params = (int)(2 * mnf::fill_net(nd, 5, sizes, 0));
-#define X(HH, NHH, KK) \
-  if (ts.H == HH && ts.NH == NHH && K == KK) return mnf::launch_tile<HH, NHH, KK>(a, inverse != 0, (hipStream_t)stream);
-  MNF_NT_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  a.cold = cold; a.cold_capacity = cold_capacity; a.rows = rows; a.T = tail_bound; a.hr = dim / 2;
+  a.n_params = (int)mnf::tile_params(dim, K, hidden);
+  return mnf::launch_tile(*r, a, inverse, (hipStream_t)stream);
 }
 
 }  // extern "C"

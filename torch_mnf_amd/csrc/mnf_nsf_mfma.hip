@@ -676,96 +676,94 @@ static void build_split_index(int32_t* idx, const int* widths = nullptr, int hr 
   }
 }
 
-template <int H, int NH, int K>
-static int launch(const float* x, float* y, float* log_det, int accumulate, const float* image,
-                  const uint32_t* simage, int64_t rows, float T, int inverse, hipStream_t stream,
-                  const float* aff = nullptr, float ld_const = 0.f, const float* scale_shift = nullptr,
-                  float* mid1 = nullptr, float* mid2 = nullptr, float* log_prob = nullptr,
-                  double* log_prob_sum = nullptr, int hr = H) {
-  const int64_t n_tiles = (rows + 15) / 16;
-  int64_t blocks = (n_tiles + kNsfWaves - 1) / kNsfWaves;
-  auto resident_of = [](auto kernel, int dev) {
-    return resident_by_occupancy(kernel, kNsfWaves * 64, dev, 2);
-  };
-  // The fp32-MFMA variants (no split image: force_fp32_mfma / MNF_FP32_MFMA=1) exist for the K = 8 shapes of full width
-  // only; an fp32 request at another shape is MNF_ERR_UNSUPPORTED here and runs the VALU kernel (fp32 too) -- the
-  // run-time-shaped kernels are split arithmetic and do not take it (mnf_generic.hip).
-  // (nor for the fused [ActNorm, Glow, NSF_CL] block: the three layers then run one after the other)
-  constexpr bool kHasFp32 = K == 8 && NH <= 16;
-  if (!simage && (!kHasFp32 || hr != H || aff)) return MNF_ERR_UNSUPPORTED;
-  static DeviceMemo memo_f32, memo_split;
-  int resident = 0;
-  if (simage) resident = memo_split.get([&](int dev) { return resident_of(nsf_mfma_kernel<H, NH, K, true, 2, true>, dev); });
-  else if constexpr (kHasFp32)
-    resident = memo_f32.get([&](int dev) { return resident_of(nsf_mfma_kernel<H, NH, K, true, 2, false>, dev); });
-  if (blocks > resident) blocks = resident;
-  const dim3 grid((unsigned)blocks), block(kNsfWaves * 64);
-#define MNF_NSF_LAUNCH_R(INVV, AFFV, SPL, RAGV)                                                                        \
-  hipLaunchKernelGGL((nsf_mfma_kernel<H, NH, K, INVV, AFFV, SPL, RAGV>), grid, block, 0, stream, x, y, log_det, image, \
-                     simage, rows, T, accumulate, aff, ld_const, scale_shift, mid1, mid2, log_prob, log_prob_sum, hr)
-#define MNF_NSF_LAUNCH(INVV, AFFV, SPL) MNF_NSF_LAUNCH_R(INVV, AFFV, SPL, false)
-  tag_kernel(simage ? (aff ? "nsf_block_split" : "nsf_mfma_split") : "nsf_mfma_fp32");
-  if (hr != H) {  // a half narrower than the tile (plain layer only)
-    if (aff) return MNF_ERR_UNSUPPORTED;
-    if (inverse) MNF_NSF_LAUNCH_R(true, 0, true, true); else MNF_NSF_LAUNCH_R(false, 0, true, true);
-  } else if (simage) {
-    if (aff) {
-      if (inverse) MNF_NSF_LAUNCH(true, 2, true); else MNF_NSF_LAUNCH(false, 1, true);
-    } else {
-      if (inverse) MNF_NSF_LAUNCH(true, 0, true); else MNF_NSF_LAUNCH(false, 0, true);
-    }
-  } else if constexpr (kHasFp32) {
-    if (inverse) MNF_NSF_LAUNCH(true, 0, false); else MNF_NSF_LAUNCH(false, 0, false);
-  }
-#undef MNF_NSF_LAUNCH
-#undef MNF_NSF_LAUNCH_R
-  return check_launch();
+// ---------------------------------------------------------------- host: the shape table
+using NsfKernel = void (*)(const float*, float*, float*, const float*, const uint32_t*, int64_t, float, int, const float*,
+                           float, const float*, float*, float*, float*, double*, int);
+enum { kNsfRagged, kNsfBlock, kNsfSplit, kNsfFp32 };  // a half narrower than the tile; the fused block; the plain layer
+struct NsfRow {
+  int H, NH, K;
+  bool fused;  // the shape has the fused [ActNorm, Glow, NSF_CL] launch
+  int64_t image_floats, split_words, plain_words;
+  void (*build_index)(int32_t*, const int*, int);
+  void (*build_split_index)(int32_t*, const int*, int);
+  NsfKernel occupancy[2];  // the instantiation whose occupancy sizes the grids of the split / the fp32 kernels
+  NsfKernel kernel[4][2];  // [kNsfRagged .. kNsfFp32][inverse, forward]
+  DeviceMemo resident[2];  // resident workgroups of the split / the fp32 kernels
+};
+// The fp32-MFMA variants (no split image: force_fp32_mfma / MNF_FP32_MFMA=1) exist for the K = 8 shapes of full width
+// only; an fp32 request at another shape is MNF_ERR_UNSUPPORTED here and runs the VALU kernel (fp32 too) -- the
+// run-time-shaped kernels are split arithmetic and do not take it (mnf_generic.hip).
+// (nor for the fused [ActNorm, Glow, NSF_CL] block: the three layers then run one after the other)
+template <int H, int NH, int K, bool FUSED>
+static NsfRow make_row() {
+  using S = NsfShape<H, NH, K>;
+  using SS = NsfSplitShape<H, NH, K>;
+  // (two initialiser lists: a shape without fp32 kernels must not instantiate one)
+  if constexpr (K == 8 && NH <= 16)
+    return {H, NH, K, FUSED, S::IMAGE_FLOATS, SS::SPLIT_WORDS, SS::PLAIN_WORDS, build_index<H, NH, K>, build_split_index<H, NH, K>,
+            {nsf_mfma_kernel<H, NH, K, true, 2, true>, nsf_mfma_kernel<H, NH, K, true, 2, false>},
+            {{nsf_mfma_kernel<H, NH, K, true, 0, true, true>, nsf_mfma_kernel<H, NH, K, false, 0, true, true>},
+             {nsf_mfma_kernel<H, NH, K, true, 2, true>, nsf_mfma_kernel<H, NH, K, false, 1, true>},
+             {nsf_mfma_kernel<H, NH, K, true, 0, true>, nsf_mfma_kernel<H, NH, K, false, 0, true>},
+             {nsf_mfma_kernel<H, NH, K, true, 0, false>, nsf_mfma_kernel<H, NH, K, false, 0, false>}}, {}};
+  else
+    return {H, NH, K, FUSED, S::IMAGE_FLOATS, SS::SPLIT_WORDS, SS::PLAIN_WORDS, build_index<H, NH, K>, build_split_index<H, NH, K>,
+            {nsf_mfma_kernel<H, NH, K, true, 2, true>, nullptr},
+            {{nsf_mfma_kernel<H, NH, K, true, 0, true, true>, nsf_mfma_kernel<H, NH, K, false, 0, true, true>},
+             {nsf_mfma_kernel<H, NH, K, true, 2, true>, nsf_mfma_kernel<H, NH, K, false, 1, true>},
+             {nsf_mfma_kernel<H, NH, K, true, 0, true>, nsf_mfma_kernel<H, NH, K, false, 0, true>}, {}}, {}};
 }
-
-// (H, NH, K) triples with an instantiated kernel
 // (three hidden layers of 32 units at dim <= 32 had kernels here until round 6: the run-time-shaped kernel of mnf_nsf_rt.hip
 // runs those within 1.1-1.2x of them, profiles/r6/coverage_map.txt)
-#define MNF_NSF_SHAPES(X) X(16, 8, 8) X(16, 16, 8) X(16, 8, 5) X(32, 8, 8) X(32, 8, 5) X(32, 16, 8) X(16, 16, 5) X(32, 16, 5) X(16, 8, 10) X(16, 16, 10)
-// ... and those that also have the fused [ActNorm, Glow, NSF_CL] variants (the affine image must be one the Glow
-// MFMA kernel supports: dim 32 and 64 are)
-#define MNF_NSF_FUSED_SHAPES(X) X(16, 8, 8) X(16, 16, 8) X(16, 8, 5) X(16, 16, 5) X(32, 8, 8) X(32, 8, 5) X(32, 16, 8)
+// fused: the affine image must be one the Glow MFMA kernel supports (dim 32 and 64 are)
+static NsfRow g_rows[] = {make_row<16, 8, 8, true>(),   make_row<16, 16, 8, true>(),  make_row<16, 8, 5, true>(),
+                          make_row<32, 8, 8, true>(),   make_row<32, 8, 5, true>(),   make_row<32, 16, 8, true>(),
+                          make_row<16, 16, 5, true>(),  make_row<32, 16, 5, false>(), make_row<16, 8, 10, false>(),
+                          make_row<16, 16, 10, false>()};
 
-// three hidden layers of at most 32 units: nh = the width the kernels run them at (8, 16 or -- dim <= 32 -- 32; narrower layers get
-// structural-zero units)
-static bool uniform_hidden3(int n_hidden, const int* hidden, int& nh) {
-  if (n_hidden != 3 || !hidden) return false;
+// The row of a layer, or null.  Three hidden layers of at most 32 units run at 8, 16 or 32 (narrower layers get
+// structural-zero units); the half at 16 or 32, the real half hr = dim / 2 narrower in whole float4 groups.
+static NsfRow* find_row(int dim, int K, int n_hidden, const int* hidden) {
+  if (n_hidden != 3 || !hidden || dim < 8 || (dim & 7) || dim > 64) return nullptr;
   int mx = 0;
   for (int i = 0; i < 3; ++i) {
-    if (hidden[i] < 1) return false;
+    if (hidden[i] < 1) return nullptr;
     mx = hidden[i] > mx ? hidden[i] : mx;
   }
-  nh = mx <= 8 ? 8 : mx <= 16 ? 16 : mx <= 32 ? 32 : 0;
-  return nh != 0;
+  const int nh = mx <= 8 ? 8 : mx <= 16 ? 16 : mx <= 32 ? 32 : 0, hp = dim / 2 <= 16 ? 16 : 32;
+  for (NsfRow& r : g_rows)
+    if (hp == r.H && nh == r.NH && K == r.K) return &r;
+  return nullptr;
 }
 
-// half width the plain-layer kernels run dim at: 16 or 32, the real half narrower in whole float4 groups (0: none)
-static int nsf_padded_half(int dim) {
-  if (dim < 8 || (dim & 7) || dim > 64) return 0;
-  return dim / 2 <= 16 ? 16 : 32;
+static int launch(NsfRow& r, const float* x, float* y, float* log_det, int accumulate, const float* image,
+                  const void* split_image, int64_t rows, float T, int inverse, int hr, hipStream_t stream,
+                  const float* aff = nullptr, float ld_const = 0.f, const float* scale_shift = nullptr,
+                  float* mid1 = nullptr, float* mid2 = nullptr, float* log_prob = nullptr,
+                  double* log_prob_sum = nullptr) {
+  const uint32_t* simage = static_cast<const uint32_t*>(split_image);
+  if (!simage && (!r.kernel[kNsfFp32][0] || hr != r.H || aff)) return MNF_ERR_UNSUPPORTED;
+  const int family = simage ? 0 : 1;
+  const int resident = r.resident[family].get(
+      [&](int dev) { return resident_by_occupancy(r.occupancy[family], kNsfWaves * 64, dev, 2); });
+  const int64_t n_tiles = (rows + 15) / 16;
+  int64_t blocks = (n_tiles + kNsfWaves - 1) / kNsfWaves;
+  if (blocks > resident) blocks = resident;
+  tag_kernel(simage ? (aff ? "nsf_block_split" : "nsf_mfma_split") : "nsf_mfma_fp32");
+  if (hr != r.H && aff) return MNF_ERR_UNSUPPORTED;  // a half narrower than the tile: the plain layer only
+  const int variant = hr != r.H ? kNsfRagged : !simage ? kNsfFp32 : aff ? kNsfBlock : kNsfSplit;
+  hipLaunchKernelGGL(r.kernel[variant][inverse ? 0 : 1], dim3((unsigned)blocks), dim3(kNsfWaves * 64), 0, stream, x, y,
+                     log_det, image, simage, rows, T, accumulate, aff, ld_const, scale_shift, mid1, mid2, log_prob,
+                     log_prob_sum, hr);
+  return check_launch();
 }
 
 int nsf_mfma_launch(const float* x, float* y, float* log_det, int accumulate, const float* image,
                     const void* split_image, int64_t rows, int dim, int K, float tail_bound, int inverse,
                     int n_hidden, const int* hidden, hipStream_t stream) {
-  int nh = 0;
-  if (!uniform_hidden3(n_hidden, hidden, nh)) return MNF_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(image) |
-       reinterpret_cast<uintptr_t>(split_image)) & 15)
-    return MNF_ERR_UNSUPPORTED;
-  const int hp = nsf_padded_half(dim);
-#define X(HH, NHH, KK) \
-  if (hp == HH && nh == NHH && K == KK) \
-    return launch<HH, NHH, KK>(x, y, log_det, accumulate, image, static_cast<const uint32_t*>(split_image), rows, \
-                               tail_bound, inverse != 0, stream, nullptr, 0.f, nullptr, nullptr, nullptr, nullptr,   \
-                               nullptr, dim / 2);
-  MNF_NSF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  NsfRow* r = find_row(dim, K, n_hidden, hidden);
+  if (!r || !aligned16(x, y, image, split_image)) return MNF_ERR_UNSUPPORTED;
+  return launch(*r, x, y, log_det, accumulate, image, split_image, rows, tail_bound, inverse, dim / 2, stream);
 }
 
 int nsf_fused_launch(const float* x, float* y, float* log_det, int accumulate, const float* image,
@@ -773,20 +771,10 @@ int nsf_fused_launch(const float* x, float* y, float* log_det, int accumulate, c
                      float* mid1, float* mid2, float* log_prob, double* log_prob_sum,
                      int64_t rows, int dim, int K, float tail_bound, int inverse, int n_hidden, const int* hidden,
                      hipStream_t stream) {
-  int nh = 0;
-  if (!uniform_hidden3(n_hidden, hidden, nh)) return MNF_ERR_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(image) |
-       reinterpret_cast<uintptr_t>(aff) | reinterpret_cast<uintptr_t>(mid1) | reinterpret_cast<uintptr_t>(mid2) |
-       reinterpret_cast<uintptr_t>(split_image)) & 15)
-    return MNF_ERR_UNSUPPORTED;
-#define X(HH, NHH, KK) \
-  if (dim == 2 * HH && nh == NHH && K == KK) \
-    return launch<HH, NHH, KK>(x, y, log_det, accumulate, image, static_cast<const uint32_t*>(split_image), rows, \
-                               tail_bound, inverse != 0, stream, aff, ld_const, scale_shift, mid1, mid2, log_prob,    \
-                               log_prob_sum);
-  MNF_NSF_FUSED_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  NsfRow* r = find_row(dim, K, n_hidden, hidden);
+  if (!r || !r->fused || dim != 2 * r->H || !aligned16(x, y, image, aff, mid1, mid2, split_image)) return MNF_ERR_UNSUPPORTED;
+  return launch(*r, x, y, log_det, accumulate, image, split_image, rows, tail_bound, inverse, r->H, stream, aff, ld_const,
+                scale_shift, mid1, mid2, log_prob, log_prob_sum);
 }
 
 }  // namespace mnf
@@ -813,60 +801,33 @@ int mnf_nsf_cl_fused(const float* x, float* y, float* log_det, int accumulate, c
 
 int mnf_nsf_cl_split_layout(int dim, int K, int n_hidden, const int* hidden, int64_t* n_split_words,
                             int64_t* n_plain_words) {
-  int nh = 0;
   if (!n_split_words || !n_plain_words || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!mnf::uniform_hidden3(n_hidden, hidden, nh)) return MNF_ERR_UNSUPPORTED;
-  const int hp = mnf::nsf_padded_half(dim);
-#define X(HH, NHH, KK)                                                   \
-  if (hp == HH && nh == NHH && K == KK) {                                \
-    *n_split_words = mnf::NsfSplitShape<HH, NHH, KK>::SPLIT_WORDS;       \
-    *n_plain_words = mnf::NsfSplitShape<HH, NHH, KK>::PLAIN_WORDS;       \
-    return MNF_OK;                                                       \
-  }
-  MNF_NSF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::NsfRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  *n_split_words = r->split_words;
+  *n_plain_words = r->plain_words;
+  return MNF_OK;
 }
 
 int mnf_nsf_cl_split_index(int dim, int K, int n_hidden, const int* hidden, int32_t* idx_host) {
-  int nh = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!mnf::uniform_hidden3(n_hidden, hidden, nh)) return MNF_ERR_UNSUPPORTED;
-  const int hp = mnf::nsf_padded_half(dim);
-#define X(HH, NHH, KK)                                              \
-  if (hp == HH && nh == NHH && K == KK) {                           \
-    mnf::build_split_index<HH, NHH, KK>(idx_host, hidden, dim / 2); \
-    return MNF_OK;                                                  \
-  }
-  MNF_NSF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::NsfRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_split_index(idx_host, hidden, dim / 2);
+  return MNF_OK;
 }
 
 int64_t mnf_nsf_cl_image_floats(int dim, int K, int n_hidden, const int* hidden) {
-  int nh = 0;
-  if (!mnf::hidden_ok(n_hidden, hidden) || !mnf::uniform_hidden3(n_hidden, hidden, nh)) return 0;
-  const int hp = mnf::nsf_padded_half(dim);
-#define X(HH, NHH, KK) \
-  if (hp == HH && nh == NHH && K == KK) return mnf::NsfShape<HH, NHH, KK>::IMAGE_FLOATS;
-  MNF_NSF_SHAPES(X)
-#undef X
-  return 0;
+  const mnf::NsfRow* r = mnf::hidden_ok(n_hidden, hidden) ? mnf::find_row(dim, K, n_hidden, hidden) : nullptr;
+  return r ? r->image_floats : 0;
 }
 
 int mnf_nsf_cl_image_index(int dim, int K, int n_hidden, const int* hidden, int32_t* idx_host) {
-  int nh = 0;
   if (!idx_host || !mnf::hidden_ok(n_hidden, hidden)) return MNF_ERR_INVALID_ARG;
-  if (!mnf::uniform_hidden3(n_hidden, hidden, nh)) return MNF_ERR_UNSUPPORTED;
-  const int hp = mnf::nsf_padded_half(dim);
-#define X(HH, NHH, KK)                                        \
-  if (hp == HH && nh == NHH && K == KK) {                     \
-    mnf::build_index<HH, NHH, KK>(idx_host, hidden, dim / 2); \
-    return MNF_OK;                                            \
-  }
-  MNF_NSF_SHAPES(X)
-#undef X
-  return MNF_ERR_UNSUPPORTED;
+  const mnf::NsfRow* r = mnf::find_row(dim, K, n_hidden, hidden);
+  if (!r) return MNF_ERR_UNSUPPORTED;
+  r->build_index(idx_host, hidden, dim / 2);
+  return MNF_OK;
 }
 
 }  // extern "C"

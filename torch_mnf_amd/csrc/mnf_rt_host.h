@@ -39,11 +39,6 @@ inline HiddenWidths scan_hidden(int n_hidden, const int* hidden, int* sizes) {
 }
 // the size class of a widest hidden layer of up to 256 units
 inline int rt_size_class(int max_width) { return max_width <= 64 ? 4 : max_width <= 128 ? 8 : 16; }
-// every pointer 16-byte aligned (a null one is): the kernels' dwordx4 row accesses
-template <typename... P>
-inline bool aligned16(const P*... p) {
-  return (((reinterpret_cast<uintptr_t>(p) & 15) == 0) && ...);
-}
 
 // ---- where a family's parameters sit in `flat`: one function per family, shared by its directions.  sizes[]: the widths
 // of the conditioner (scan_hidden).  Each fills the layout part of the kernel arguments and returns the parameter count;
