@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 30
+#define MNF_ABI_VERSION 31
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -174,6 +174,21 @@ int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const fl
  * only, as mnf_affine_half_stack), n_layers 1 .. 32.  0 for a half narrower than its tile (the ragged variant has no
  * noise source) and for every shape without a split stack kernel. */
 int mnf_affine_half_stack_sample_supported(int dim, int n_hidden, const int* hidden_host, int n_layers);
+/* mnf_affine_half_stack_sample that also writes the sample's own log-density (kernel family "ahf_split_stack_sample_lq"):
+ *   log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r) = -|z_r|^2 / 2 - dim / 2 log(2 pi) - sum_layers log|det J|,
+ * the model's density at y_r ("sample and log-prob" in one pass: importance weights, entropy / KL estimates, the
+ * reverse-KL objective) from the noise and the per-layer s values while both are in registers: 4*dim + 4 bytes per row of
+ * HBM traffic, no inverse pass.  y is bit for bit mnf_affine_half_stack_sample's; log_q[r] is a pure function of (seed,
+ * row0 + r, parameters) too -- a row does not depend on the batch it is part of (the kernel's header comment gives the
+ * fp32 order of the sum).  Argument checks as mnf_affine_half_stack_sample, plus MNF_ERR_INVALID_ARG for a NULL log_q or
+ * one that is not 4-byte aligned.  rows == 0: MNF_OK, nothing is touched.  MNF_ERR_UNSUPPORTED where
+ * mnf_affine_half_stack_sample_logq_supported() is 0 or y is not 16-byte aligned (caller: mnf_normal_rows_sq, the ordinary
+ * forward pass, mnf_gauss_logq_sq).  Never allocates or synchronises; capturable. */
+int mnf_affine_half_stack_sample_logq(uint64_t seed, int64_t row0, float* y, float* log_q, const float* images,
+                                      const void* split_images, const int* parity_host, int n_layers, int64_t rows, int dim,
+                                      int n_hidden, const int* hidden_host, void* stream);
+/* The shapes of mnf_affine_half_stack_sample_supported (every one of them has a log-q instantiation). */
+int mnf_affine_half_stack_sample_logq_supported(int dim, int n_hidden, const int* hidden_host, int n_layers);
 /* n_layers (1 .. 32) AffineHalfFlow layers of one shape WITHOUT a per-shape kernel in ONE launch of the run-time-shaped
  * kernel (mnf_ahf_rt.hip; kernel family "ahf_stack_rt", "ahf_rt" for one layer).  flats: the layers' plain parameter
  * vectors back to back, layer 0 first, mnf_affine_half_flat_floats() each -- no operand image, no index table.  Layers
@@ -401,6 +416,16 @@ int mnf_sample_z0_noise(uint64_t seed, float* eps, int64_t rows, int dim, void* 
  * draws them.  mnf_sample_z0_noise is row0 == 0; mnf_affine_half_stack_sample generates exactly these numbers in place.
  * MNF_ERR_INVALID_ARG for NULL out, rows < 0, row0 < 0, dim < 1. */
 int mnf_normal_rows(uint64_t seed, int64_t row0, float* out, int64_t rows, int dim, void* stream);
+/* mnf_normal_rows that also writes sqnorm[r] = sum_c out[r][c]^2 (rows,), in fp32 from the values while they are in
+ * registers (no second pass over out).  out is bit for bit mnf_normal_rows'.  A kernel of its own: a lane owns whole
+ * Box-Muller pairs and stores 8 or 16 bytes at a time where dim and the alignment of out allow.  MNF_ERR_INVALID_ARG for
+ * NULL out / sqnorm, rows < 0, row0 < 0, dim < 1; rows == 0: MNF_OK. */
+int mnf_normal_rows_sq(uint64_t seed, int64_t row0, float* out, float* sqnorm, int64_t rows, int dim, void* stream);
+/* log q of a sample from the |z|^2 of its noise and the forward pass's log_det:
+ *   log_q[r] = (-z_sqnorm[r] / 2 - dim / 2 log(2 pi)) - log_det[r]
+ * (mnf_gauss_logprob_sq is the inverse pass's form, + log_det).  MNF_ERR_INVALID_ARG for a NULL pointer, rows < 0, dim < 1;
+ * rows == 0: MNF_OK. */
+int mnf_gauss_logq_sq(const float* z_sqnorm, const float* log_det, float* log_q, int64_t rows, int dim, void* stream);
 /* mnf_sample_z0_bwd (eps != NULL) / mnf_sample_z0_seeded_bwd (eps == NULL) with the sums over the rows added in a fixed
  * order: every row block leaves its sums in `workspace` (mnf_sample_z0_bwd_workspace(rows, dim) floats) and a second
  * launch adds the blocks up in order -- no float atomics, the result repeats bit for bit (MNF_DETERMINISTIC=1). */

@@ -65,6 +65,8 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 | NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
 | NormalizingFlowModel.sample(seed=) | any    | the model is ONE run of AffineHalfFlow layers on ahf_split_stack's full-tile shapes (d / 2 in 16/32/64/128) | ahf_split_stack_sample (one launch, noise in-kernel) |
 |                          | else            | anything (StandardNormal base)                    | mnf_normal_rows' noise launch, then forward's rows above without intermediates |
+| sample(seed=, return_log_prob=True) | any   | as the one-launch row above, no gradients wanted  | ahf_split_stack_sample_lq (one launch: x and log_q) |
+|                          | else            | anything (StandardNormal base); any model when gradients are wanted | mnf_normal_rows_sq (noise + |z|^2), forward's rows above without intermediates, mnf_gauss_logq_sq |
 | MNFConv2d.forward        | MNF_CONV_FUSED (opt-in: False) | n_out <= 64, n_in k^2 <= 4096          | mnf_conv_fwd (one launch behind the operands) |
 |                          | else            | anything                                          | MIOpen convolutions between the library's operand and noise launches |
 | MNFConv2d.forward bwd    | MNF_CONV_BWD_FUSED (opt-in: False), on mnf_conv_fwd's node | weights: mnf_conv_fwd's shapes; input: those with n_in <= 64, n_out k^2 <= 4096 | mnf_conv_bwd_weight / mnf_conv_bwd_input |
@@ -94,7 +96,11 @@ The sample(seed=) rows are NormalizingFlowModel.sample with a seed (no row-count
 and forward, as ever): rows first_row .. first_row + n - 1 of forward(z), z[r, c] = z0_normal(seed, r, c).  The one-launch
 row needs the run on the split per-shape route with its images ready (no force_generic, no fp32 request, run fusion on, no
 per-launch event marks) and mnf_affine_half_stack_sample_supported(); both rows compute the same sample, and a model takes
-the same row at every call of one shape.
+the same row at every call of one shape.  With return_log_prob=True the same choice is made with
+mnf_affine_half_stack_sample_logq_supported() (the same shapes); log_q[r] = log N(z_r) - log_det_forward(z_r) comes out of
+the stack launch, or on the general row from |z|^2 (summed in the noise launch's registers) and forward's log_det.  A call
+with grad mode on and a parameter that requires grad takes the general row whatever the model: the pass then runs through
+the layers' autograd nodes (there is no gradient kernel for the one launch), with gauss_logq_sq's formula as tensor ops.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and

@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 30  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 31  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -42,6 +42,9 @@ SIGNATURES = {
     "mnf_affine_half_stack_sample": (c_int, [c_uint64, c_int64, c_void_p, c_void_p, c_void_p, _intp, c_int, c_int64, c_int,
                                              c_int, _intp, c_void_p]),
     "mnf_affine_half_stack_sample_supported": (c_int, [c_int, c_int, _intp, c_int]),
+    "mnf_affine_half_stack_sample_logq": (c_int, [c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, _intp, c_int,
+                                                  c_int64, c_int, c_int, _intp, c_void_p]),
+    "mnf_affine_half_stack_sample_logq_supported": (c_int, [c_int, c_int, _intp, c_int]),
     "mnf_affine_half_split_layout": (c_int, [c_int, c_int, _intp, c_int, c_int, _i64p, _i64p]),
     "mnf_affine_half_split_index": (c_int, [c_int, c_int, _intp, c_int, c_int, _i32p]),
     "mnf_pack_gather_split": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
@@ -206,6 +209,8 @@ SIGNATURES = {
     "mnf_sample_z0_seeded_bwd": (c_int, [c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_sample_z0_noise": (c_int, [c_uint64, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_normal_rows": (c_int, [c_uint64, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "mnf_normal_rows_sq": (c_int, [c_uint64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "mnf_gauss_logq_sq": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "mnf_sample_z0_bwd_workspace": (c_int64, [c_int64, c_int]),
     "mnf_sample_z0_bwd_det": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
                                       c_int64, c_void_p]),

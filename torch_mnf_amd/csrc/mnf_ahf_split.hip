@@ -278,13 +278,29 @@ __device__ __forceinline__ void half_store4(float* p, int col, int h, bool vec, 
 // (low word) and `h_ragged` (high word); mid, log_det, ysq, log_prob and log_prob_sum are NULL.  A compile-time switch,
 // not a run-time row source in the forward instantiations: as a run-time branch at the top of the group loop it cost the
 // forward kernels 2 .. 10 VGPRs and spills in the two hidden-32 ones that sit at 256 (profiles/r28/kernel_resources.txt).
-template <int H, int HID, bool INV, bool RAG, bool SAMPLE = false>
+//
+// LQ (with SAMPLE: mnf_affine_half_stack_sample_logq) also writes the sample's own log-density, 4 more bytes per row:
+//   log_q[r] = log N(z_r; 0, I) - sum_layers log|det J| = -|z_r|^2 / 2 - d/2 log(2 pi) - log_det_forward(z_r),
+// into the `log_prob` argument (NULL in every other SAMPLE launch: the sixteen arguments are all taken).  |z|^2 is of the
+// GENERATED noise, not of the output, so it has to survive the layers: it costs no register of its own because the
+// per-lane log-det partial ld[t], which every forward instantiation carries through the layer loop anyway, starts from it
+// instead of from 0.  The exact fp32 order, per lane (row r, quarter q; a lane holds 8 G of the row's 2 H numbers):
+//   a = 0;  for g in 0 .. G-1, e in 0 .. 3:  a = fma(lo[g][e], lo[g][e], a)      (columns 16 g + 4 q + e)
+//           for g in 0 .. G-1, e in 0 .. 3:  a = fma(hi[g][e], hi[g][e], a)      (columns H + 16 g + 4 q + e)
+//   ld = 0.5 * a;  every layer, in model order: ld += (its s values in the layer kernel's own order: ahf_transform, or the
+//   chunked emit at d = 256, or the cold fp32 fall-back -- all three add to this one partial)
+//   l = sum_over_q(ld)  (ld + lane^16's, then + lane^32's);  log_q[r] = -l - (float)dim * kHalfLog2Pi
+// A row's value depends on (seed, row, parameters) alone: not on the batch it is part of, nor on where that batch ends.
+// Its own instantiations, not a run-time `if (log_prob)` in the nine SAMPLE ones: those serve the x-only launch as the
+// parent's instruction streams (profiles/r30/isa_diff.txt).
+template <int H, int HID, bool INV, bool RAG, bool SAMPLE = false, bool LQ = false>
 __global__ void __launch_bounds__(stack_waves<H>() * 64, stack_waves_per_simd<H>())
 ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ mid,
                        float* __restrict__ log_det, float* __restrict__ ysq, const uint32_t* __restrict__ simages,
                        const float* __restrict__ images_f32, uint32_t parity_bits, int n_layers, int64_t rows,
                        int accumulate, float* __restrict__ log_prob, double* __restrict__ log_prob_sum, int h_ragged,
                        int vec_ok) {
+  static_assert(!LQ || SAMPLE, "log q is the density of the noise the kernel generated");
   using S = SplitShape<H, HID>;
   constexpr int G = S::G, NTL = stack_tiles<H>(), kStackWaves = stack_waves<H>();
   const int h = RAG ? h_ragged : H, dim = 2 * h;  // the rows in memory are 2 h wide; the tiles H
@@ -309,6 +325,7 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
     int64_t row[NTL], rowc[NTL];
     bool live[NTL];
     f32x4 lo[NTL][G], hi[NTL][G];
+    float zsq_half[LQ ? NTL : 1];  // LQ: |z|^2 / 2 of the lane's generated numbers (see the header comment)
 #pragma unroll
     for (int t = 0; t < NTL; ++t) {
       row[t] = (int64_t)grp * GROUP_ROWS + (wave * NTL + t) * 16 + j;
@@ -335,6 +352,18 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
         for (int g = 0; g < G; ++g) lo[t][g] = quad(8 * g + 2 * qs);
 #pragma unroll
         for (int g = 0; g < G; ++g) hi[t][g] = quad(H / 2 + 8 * g + 2 * qs);
+        if constexpr (LQ) {
+          float a = 0.f;
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a = fmaf(lo[t][g][r], lo[t][g][r], a);
+#pragma unroll
+          for (int g = 0; g < G; ++g)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a = fmaf(hi[t][g][r], hi[t][g][r], a);
+          zsq_half[t] = 0.5f * a;
+        }
       } else {
         const float* xr = x + rowc[t] * dim;
 #pragma unroll
@@ -348,7 +377,10 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
     __syncthreads();  // (hipcc drains vmcnt before a barrier: image and rows have landed)
     float ld[NTL];
 #pragma unroll
-    for (int t = 0; t < NTL; ++t) ld[t] = 0.f;
+    for (int t = 0; t < NTL; ++t) {
+      if constexpr (LQ) ld[t] = zsq_half[t];
+      else ld[t] = 0.f;
+    }
     for (int li = 0; li < n_layers; ++li) {
       const int layer = layer_at(li);
       if (li + 1 < n_layers)  // next layer's image into the other buffer, in flight under this layer's math
@@ -434,6 +466,12 @@ ahf_split_stack_kernel(const float* __restrict__ x, float* __restrict__ y, float
         for (int g = 0; g < G; ++g) half_store4<RAG>(yr, 16 * g + 4 * q, h, vec, lo[t][g]);
 #pragma unroll
         for (int g = 0; g < G; ++g) half_store4<RAG>(yr + h, 16 * g + 4 * q, h, vec, hi[t][g]);
+      }
+      if constexpr (LQ) {
+        // (inside SAMPLE `accumulate` carries row0 and the generic epilogue below would use |y|^2: neither applies)
+        const float l = sum_over_q(ld[t]);
+        if (live[t] && q == 0) log_prob[row[t]] = -l - (float)dim * kHalfLog2Pi;
+        continue;
       }
       float ld_row = 0.f;
       if (log_det) {
@@ -578,12 +616,13 @@ static SplitRow g_split_rows[] = {make_split_row<16, 24>(), make_split_row<32, 2
                                   make_split_row<16, 64>(), make_split_row<32, 64>(),  make_split_row<64, 64>()};
 
 // ... and the rows of the stack kernel: one per pair with its four variants by (full tiles / narrow half) and direction,
-// then one per pair for the sample launch, which runs the SAMPLE instantiation on the same grid.
+// then one per pair for the sample launch, which runs the SAMPLE instantiation on the same grid, and one per pair for the
+// sample launch that also writes log q (SAMPLE and LQ).
 using StackKernel = void (*)(const float*, float*, float*, float*, float*, const uint32_t*, const float*, uint32_t, int,
                              int64_t, int, float*, double*, int, int);
 struct StackRow {
   int H, HID;
-  bool sample;
+  bool sample, logq;
   int waves, group_rows;
   size_t lds_bytes;          // the dynamic part of the two images (see the kernel)
   int per_cu;                // workgroups a CU holds
@@ -591,7 +630,7 @@ struct StackRow {
   DeviceMemo resident[2];    // [ragged], per device: 0 = not set up yet, -1 = the dynamic-LDS attribute could not be set,
                              // else the number of resident workgroups
 };
-template <int H, int HID, bool SAMPLE = false>
+template <int H, int HID, bool SAMPLE = false, bool LQ = false>
 static StackRow make_stack_row() {
   constexpr size_t image_bytes = 2 * SplitShape<H, HID>::IMAGE_WORDS * sizeof(uint32_t);
   constexpr size_t lds_bytes = image_bytes <= 64 * 1024 ? 0 : image_bytes;
@@ -601,10 +640,10 @@ static StackRow make_stack_row() {
   int per_cu = 4 * stack_waves_per_simd<H>() / waves;
   while (per_cu > 1 && per_cu * image_bytes > 160 * 1024) --per_cu;
   if constexpr (SAMPLE)
-    return {H, HID, true, waves, group_rows, lds_bytes, per_cu,
-            {{nullptr, ahf_split_stack_kernel<H, HID, false, false, true>}, {}}, {}};
+    return {H, HID, true, LQ, waves, group_rows, lds_bytes, per_cu,
+            {{nullptr, ahf_split_stack_kernel<H, HID, false, false, true, LQ>}, {}}, {}};
   else
-    return {H, HID, false, waves, group_rows, lds_bytes, per_cu,
+    return {H, HID, false, false, waves, group_rows, lds_bytes, per_cu,
             {{ahf_split_stack_kernel<H, HID, true, false>, ahf_split_stack_kernel<H, HID, false, false>},
              {ahf_split_stack_kernel<H, HID, true, true>, ahf_split_stack_kernel<H, HID, false, true>}}, {}};
 }
@@ -616,21 +655,24 @@ static StackRow g_stack_rows[] = {
     make_stack_row<16, 32>(),       make_stack_row<32, 32>(),       make_stack_row<64, 32>(),
     make_stack_row<16, 24, true>(), make_stack_row<32, 24, true>(), make_stack_row<16, 16, true>(),
     make_stack_row<32, 16, true>(), make_stack_row<64, 24, true>(), make_stack_row<128, 24, true>(),
-    make_stack_row<16, 32, true>(), make_stack_row<32, 32, true>(), make_stack_row<64, 32, true>()};
+    make_stack_row<16, 32, true>(), make_stack_row<32, 32, true>(), make_stack_row<64, 32, true>(),
+    make_stack_row<16, 24, true, true>(), make_stack_row<32, 24, true, true>(),  make_stack_row<16, 16, true, true>(),
+    make_stack_row<32, 16, true, true>(), make_stack_row<64, 24, true, true>(),  make_stack_row<128, 24, true, true>(),
+    make_stack_row<16, 32, true, true>(), make_stack_row<32, 32, true, true>(),  make_stack_row<64, 32, true, true>()};
 
 // the stack table's row of a tile half and hidden width, or null
-static StackRow* stack_row(int hp, int hid, bool sample = false) {
+static StackRow* stack_row(int hp, int hid, bool sample = false, bool logq = false) {
   for (StackRow& r : g_stack_rows)
-    if (hp == r.H && hid == r.HID && sample == r.sample) return &r;
+    if (hp == r.H && hid == r.HID && sample == r.sample && logq == r.logq) return &r;
   return nullptr;
 }
 // The stack kernel's row for layers of `dim` columns run at hidden width `hid` (ahf_padded_hidden), or null.  h = dim / 2;
 // h < row->H: a narrow half, which only the ragged variant runs.
-static StackRow* find_stack_row(int dim, int hid, int n_layers, int& h, bool sample = false) {
+static StackRow* find_stack_row(int dim, int hid, int n_layers, int& h, bool sample = false, bool logq = false) {
   h = dim / 2;
   const int hp = (dim & 1) ? 0 : ahf_padded_half(h);
   if (hid == 32 && h == hp && hp <= 32 && n_layers > 1) return nullptr;  // measured: no faster than layer by layer
-  return stack_row(hp, hid, sample);
+  return stack_row(hp, hid, sample, logq);
 }
 // The row of a layer's split image, or null.  Full tiles: every split shape; a narrow half: the shapes of the stack kernel
 // (its only kernel).
@@ -672,7 +714,7 @@ static int launch_split_stack(StackRow& r, bool ragged, int inverse, const float
   if (resident <= 0) return MNF_ERR_UNSUPPORTED;
   const int64_t n_groups = (rows + r.group_rows - 1) / r.group_rows;
   const dim3 grid((unsigned)(n_groups < resident ? n_groups : resident)), block(r.waves * 64);
-  tag_kernel(r.sample ? "ahf_split_stack_sample" : "ahf_split_stack");
+  tag_kernel(r.logq ? "ahf_split_stack_sample_lq" : r.sample ? "ahf_split_stack_sample" : "ahf_split_stack");
   hipLaunchKernelGGL(r.kernel[ragged][inverse ? 0 : 1], grid, block, r.lds_bytes, stream, x, y, mid, log_det, ysq,
                      static_cast<const uint32_t*>(split_images), images, parity_bits, n_layers, rows, accumulate,
                      log_prob, log_prob_sum, h, vec_ok);
@@ -695,10 +737,29 @@ int ahf_split_stack_launch(const float* x, float* y, float* mid, float* log_det,
 
 // The shapes with a sample launch: the stack kernel's full-tile forward instantiations (a narrow half runs on the ragged
 // variant, which has no noise source), under the stack launcher's own rule for hidden width 32.
-static StackRow* find_sample_row(int dim, int hid, int n_layers) {
+static StackRow* find_sample_row(int dim, int hid, int n_layers, bool logq = false) {
   int h = 0;
-  StackRow* r = n_layers < 1 || n_layers > 32 ? nullptr : find_stack_row(dim, hid, n_layers, h, true);
+  StackRow* r = n_layers < 1 || n_layers > 32 ? nullptr : find_stack_row(dim, hid, n_layers, h, true, logq);
   return r && h == r->H ? r : nullptr;
+}
+
+// the two sample entries: the SAMPLE (and LQ) instantiation on the stack launch's grid -- seed rides in x, row0 in
+// accumulate | h << 32, log_q in log_prob (see the kernel)
+static int sample_launch(bool logq, uint64_t seed, int64_t row0, float* y, float* log_q, const float* images,
+                         const void* split_images, const int* parity_host, int n_layers, int64_t rows, int dim,
+                         int n_hidden, const int* hidden_host, void* stream) {
+  if (!y || !images || !split_images || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || row0 < 0 ||
+      dim < 2 || (dim & 1) || !hidden_ok(n_hidden, hidden_host) ||
+      (logq && (!log_q || (reinterpret_cast<uintptr_t>(log_q) & 3))))
+    return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  uint32_t bits = 0;
+  for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
+  StackRow* r = find_sample_row(dim, ahf_padded_hidden(n_hidden, hidden_host), n_layers, logq);
+  if (!r || !aligned16(y, split_images, images)) return MNF_ERR_UNSUPPORTED;
+  return launch_split_stack(*r, false, 0, reinterpret_cast<const float*>(seed), y, nullptr, nullptr, nullptr,
+                            split_images, images, bits, n_layers, rows, (int)(uint32_t)row0, log_q, nullptr,
+                            (int)(uint32_t)((uint64_t)row0 >> 32), 1, (hipStream_t)stream);
 }
 
 }  // namespace mnf
@@ -713,18 +774,20 @@ int mnf_affine_half_stack_sample_supported(int dim, int n_hidden, const int* hid
 int mnf_affine_half_stack_sample(uint64_t seed, int64_t row0, float* y, const float* images, const void* split_images,
                                  const int* parity_host, int n_layers, int64_t rows, int dim, int n_hidden,
                                  const int* hidden_host, void* stream) {
-  if (!y || !images || !split_images || !parity_host || n_layers < 1 || n_layers > 32 || rows < 0 || row0 < 0 ||
-      dim < 2 || (dim & 1) || !mnf::hidden_ok(n_hidden, hidden_host))
-    return MNF_ERR_INVALID_ARG;
-  if (rows == 0) return MNF_OK;
-  uint32_t bits = 0;
-  for (int l = 0; l < n_layers; ++l) bits |= (parity_host[l] ? 1u : 0u) << l;
-  mnf::StackRow* r = mnf::find_sample_row(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers);
-  if (!r || !mnf::aligned16(y, split_images, images)) return MNF_ERR_UNSUPPORTED;
-  // the SAMPLE instantiation on the stack launch's grid: seed rides in x, row0 in accumulate | h << 32 (see the kernel)
-  return mnf::launch_split_stack(*r, false, 0, reinterpret_cast<const float*>(seed), y, nullptr, nullptr,
-                                 nullptr, split_images, images, bits, n_layers, rows, (int)(uint32_t)row0, nullptr, nullptr,
-                                 (int)(uint32_t)((uint64_t)row0 >> 32), 1, (hipStream_t)stream);
+  return mnf::sample_launch(false, seed, row0, y, nullptr, images, split_images, parity_host, n_layers, rows, dim, n_hidden,
+                            hidden_host, stream);
+}
+
+int mnf_affine_half_stack_sample_logq_supported(int dim, int n_hidden, const int* hidden_host, int n_layers) {
+  return mnf::hidden_ok(n_hidden, hidden_host) &&
+         mnf::find_sample_row(dim, mnf::ahf_padded_hidden(n_hidden, hidden_host), n_layers, true) != nullptr;
+}
+
+int mnf_affine_half_stack_sample_logq(uint64_t seed, int64_t row0, float* y, float* log_q, const float* images,
+                                      const void* split_images, const int* parity_host, int n_layers, int64_t rows, int dim,
+                                      int n_hidden, const int* hidden_host, void* stream) {
+  return mnf::sample_launch(true, seed, row0, y, log_q, images, split_images, parity_host, n_layers, rows, dim, n_hidden,
+                            hidden_host, stream);
 }
 
 int mnf_affine_half_split_layout(int dim, int n_hidden, const int* hidden, int has_scale, int has_shift,

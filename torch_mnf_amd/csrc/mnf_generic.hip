@@ -639,6 +639,66 @@ __global__ void sample_z0_noise_kernel(uint64_t seed, float* __restrict__ eps, i
   if (i < rows * dim) eps[i] = z0_normal(seed, row0 + i / dim, (int)(i % dim));
 }
 
+// The same numbers with the row's |z|^2 from the values while they are in registers (mnf_normal_rows_sq: the general
+// route of sample(..., return_log_prob=True)).  A lane owns whole Box-Muller pairs -- four consecutive columns 4 k .. 4 k + 3
+// = pairs 2 k, 2 k + 1 per step, each pair evaluated once (the kernel above is one thread per element and evaluates every
+// pair twice) -- and lpr lanes (a power of two, >= the row's quads up to 64) share a row, 64 / lpr rows per wave.
+// Stores: 16 bytes where dim % 4 == 0 and `out` is 16-byte aligned (VEC = 4), 8 bytes where dim is even and `out` 8-byte
+// aligned (VEC = 2), else element by element; the odd last column of an odd dim is the first half of its pair.
+// sqnorm[r], the exact fp32 order: per lane a = 0, then a = fma(v, v, a) over its columns in ascending order (k = l,
+// l + lpr, ...); then a += lane^off's for off = lpr / 2, lpr / 4, .., 1.
+template <int VEC>
+__global__ void __launch_bounds__(kThreads) normal_rows_sq_kernel(uint64_t seed, int64_t row0, float* __restrict__ out,
+                                                                  float* __restrict__ sqnorm, int64_t rows, int dim) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n_waves = (int64_t)gridDim.x * (kThreads / 64);
+  const int quads = (dim + 3) >> 2;
+  int lpr = 1;
+  while (lpr < 64 && lpr < quads) lpr <<= 1;
+  const int rpw = 64 / lpr;
+  const int sub = lane / lpr, l = lane % lpr;
+  for (int64_t base = ((int64_t)blockIdx.x * (kThreads / 64) + wave) * rpw; base < rows; base += n_waves * rpw) {
+    const int64_t row = base + sub;
+    float acc = 0.f;
+    if (row < rows) {
+      const uint32_t rh = z0_row_hash(seed, row0 + row);
+      float* o = out + row * dim;
+      for (int k = l; k < quads; k += lpr) {
+        const int c = 4 * k;  // (c < dim)
+        float n[4] = {0.f, 0.f, 0.f, 0.f};
+        z0_normal_pair(rh, (uint32_t)seed, 2 * k, n[0], n[1]);
+        if (c + 2 < dim) z0_normal_pair(rh, (uint32_t)seed, 2 * k + 1, n[2], n[3]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+          if (c + e < dim) acc = fmaf(n[e], n[e], acc);
+        if (VEC == 4) {
+          *reinterpret_cast<float4*>(o + c) = make_float4(n[0], n[1], n[2], n[3]);
+        } else if (VEC == 2) {  // (dim even: a pair is inside or outside as a whole)
+          *reinterpret_cast<float2*>(o + c) = make_float2(n[0], n[1]);
+          if (c + 2 < dim) *reinterpret_cast<float2*>(o + c + 2) = make_float2(n[2], n[3]);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (c + e < dim) o[c + e] = n[e];
+        }
+      }
+    }
+    for (int off = lpr >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+    if (row < rows && l == 0) sqnorm[row] = acc;
+  }
+}
+
+// log q of a sample from the |z|^2 of its noise and the forward pass's log_det: log N(z; 0, I) - log_det.  The mirror of
+// gauss_logprob_sq_kernel (log N + log_det of the inverse pass) without its sum.
+__global__ void __launch_bounds__(kThreads) gauss_logq_sq_kernel(const float* __restrict__ zsq,
+                                                                 const float* __restrict__ log_det,
+                                                                 float* __restrict__ log_q, int64_t rows, int dim) {
+  const float cst = (float)dim * kHalfLog2Pi;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += stride)
+    log_q[r] = (-0.5f * zsq[r] - cst) - log_det[r];
+}
+
 // gradients of the prologue: d mean[j] = sum_r g[r][j];  d log_var[j] = sum_r g[r][j] eps[r][j] * 0.5 sqrt(exp(log_var[j])).
 // blockDim = (64 lanes, 4 row lanes); a lane owns VEC consecutive dims (VEC = 4: 16-byte loads, a wave reads 1 KB of a
 // row at a time -- with 4-byte loads the 1.64 GB pass ran at half the HBM rate); a workgroup takes 64 VEC dims and the
@@ -1500,6 +1560,29 @@ int mnf_normal_rows(uint64_t seed, int64_t row0, float* out, int64_t rows, int d
   if (rows == 0) return MNF_OK;
   hipLaunchKernelGGL(sample_z0_noise_kernel, dim3((unsigned)((rows * dim + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seed,
                      out, rows, dim, row0);
+  return check_launch();
+}
+
+int mnf_normal_rows_sq(uint64_t seed, int64_t row0, float* out, float* sqnorm, int64_t rows, int dim, void* stream) {
+  if (!out || !sqnorm || rows < 0 || row0 < 0 || dim < 1) return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  const int quads = (dim + 3) / 4;
+  int lpr = 1;
+  while (lpr < 64 && lpr < quads) lpr <<= 1;
+  // one wave per 64 / lpr rows, walking on from a grid that fills the chip a few times over
+  const dim3 grid(grid_for((rows + 64 / lpr - 1) / (64 / lpr), kThreads / 64, 8192)), block(kThreads);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(out);
+  auto kernel = dim % 4 == 0 && !(a & 15) ? normal_rows_sq_kernel<4>
+                : dim % 2 == 0 && !(a & 7) ? normal_rows_sq_kernel<2> : normal_rows_sq_kernel<1>;
+  hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, seed, row0, out, sqnorm, rows, dim);
+  return check_launch();
+}
+
+int mnf_gauss_logq_sq(const float* z_sqnorm, const float* log_det, float* log_q, int64_t rows, int dim, void* stream) {
+  if (!z_sqnorm || !log_det || !log_q || rows < 0 || dim < 1) return MNF_ERR_INVALID_ARG;
+  if (rows == 0) return MNF_OK;
+  hipLaunchKernelGGL(gauss_logq_sq_kernel, dim3(grid_for(rows, 4 * kThreads, 256)), dim3(kThreads), 0,
+                     (hipStream_t)stream, z_sqnorm, log_det, log_q, rows, dim);
   return check_launch();
 }
 

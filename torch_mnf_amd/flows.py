@@ -2346,6 +2346,7 @@ class _AffineRun:
         self._rt_bwd_ok = None    # mnf_affine_half_bwd_rt_stack_supported, asked once
         self._rt_bwd_wide_ok = None  # mnf_affine_half_bwd_rt_wide_stack_supported, asked once
         self._sample_ok = None    # mnf_affine_half_stack_sample_supported, asked once
+        self._sample_lq_ok = None  # mnf_affine_half_stack_sample_logq_supported, asked once
         self._rt_now = False      # the call in flight trains on the run-time-shaped route (launch_grad -> _AffineRunFn)
         # the owner's switch (NormalizingFlow / FusedAffineStack .fuse_rt_training), copied here before every pass
         self.fuse_rt_training = False
@@ -2529,6 +2530,32 @@ class _AffineRun:
             return None
         _lib.check("mnf_affine_half_stack_sample", rc)
         return y
+
+    def launch_sample_logq(self, seed: int, first_row: int, rows: int, device,
+                           images: tuple | None) -> tuple[Tensor, Tensor] | None:
+        """``launch_sample`` that also returns the rows' own log-density: ONE ``mnf_affine_half_stack_sample_logq``
+        launch writes x and log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r) (4 more bytes per row).  None under
+        ``launch_sample``'s conditions, by this entry's own shape query (the caller then takes the general route)."""
+        f0, n = self.layers[0], len(self.layers)
+        if images is None or isinstance(images[0], str) or images[1] is None or self._sample_lq_ok is False:
+            return None
+        if self._sample_lq_ok is None:
+            self._sample_lq_ok = bool(_lib.load().mnf_affine_half_stack_sample_logq_supported(
+                f0.dim, len(f0.h_sizes), f0._hid, n))
+            if not self._sample_lq_ok:
+                return None
+        y = torch.empty((rows, f0.dim), dtype=torch.float32, device=device)
+        log_q = torch.empty(rows, dtype=torch.float32, device=device)
+        par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
+        with torch.cuda.device(y.device):
+            rc = _lib.load().mnf_affine_half_stack_sample_logq(
+                ctypes.c_uint64(seed), first_row, y.data_ptr(), log_q.data_ptr(), images[0].data_ptr(),
+                images[1].data_ptr(), par, n, rows, f0.dim, len(f0.h_sizes), f0._hid, _stream())
+        if rc == _lib.MNF_ERR_UNSUPPORTED:
+            self._sample_lq_ok = False
+            return None
+        _lib.check("mnf_affine_half_stack_sample_logq", rc)
+        return y, log_q
 
     def usable(self, x) -> bool:
         return self.ready(x) is not None
@@ -3134,6 +3161,16 @@ class StandardNormal:
                     _stream()))
         return out
 
+    def _sample_sq(self, rows: int, seed: int, first_row: int) -> tuple[Tensor, Tensor]:
+        """The seeded rows with their |z|^2 (``mnf_normal_rows_sq``: one launch, the squares summed in registers);
+        the rows are bit for bit ``sample((rows,), seed=, first_row=)``.  Arguments already validated, rows > 0."""
+        out = torch.empty((rows, self.dim), dtype=torch.float32, device=self.device)
+        sq = torch.empty(rows, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(out.device):
+            _lib.check("mnf_normal_rows_sq", _lib.load().mnf_normal_rows_sq(
+                ctypes.c_uint64(seed), first_row, out.data_ptr(), sq.data_ptr(), rows, self.dim, _stream()))
+        return out, sq
+
 
 class NormalizingFlowModel(NormalizingFlow):
     """(base distribution, flows) pair (flows/core.py:38-55), plus a fused ``log_prob``."""
@@ -3146,7 +3183,7 @@ class NormalizingFlowModel(NormalizingFlow):
         zs, _ = self._pass(x, True, last_only=True)  # z and only z: no intermediate is written
         return self.base.log_prob(zs[-1])
 
-    def sample(self, *num_samples: int, seed: int | None = None, first_row: int = 0) -> Tensor:
+    def sample(self, *num_samples: int, seed: int | None = None, first_row: int = 0, return_log_prob: bool = False):
         """Without ``seed``: the reference's sample (core.py:51-55) -- the base's draw from torch's generator, then
         ``forward``.
 
@@ -3156,13 +3193,29 @@ class NormalizingFlowModel(NormalizingFlow):
         (seed, row, parameters): chunks and per-rank row ranges of one seed concatenate to the whole.  A model that is
         one run of AffineHalfFlow layers on the split per-shape stack kernel draws the noise inside that kernel -- ONE
         launch that reads no row tensor and writes only x (``ahf_split_stack_sample``); every other model materialises
-        the noise and runs the pass without intermediates.  Both routes compute the same sample."""
+        the noise and runs the pass without intermediates.  Both routes compute the same sample.
+
+        ``return_log_prob=True`` returns ``(x, log_q)``: log_q (n,) fp32 is the model's density at its own sample,
+        log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r) -- mathematically ``log_prob(x)[r]``, from the ONE forward pass
+        that produced x (``log_prob(x)`` runs every layer again, in the inverse direction).  x is the x of the same call
+        without the flag.  With ``seed`` log_q is a pure function of (seed, row, parameters) as x is, so pieces
+        concatenate; the one-launch models write it from the same launch (``ahf_split_stack_sample_lq``), every other
+        model takes ``mnf_normal_rows_sq`` (noise and its |z|^2), the pass, and ``mnf_gauss_logq_sq``.  When grad mode is
+        on and a parameter requires grad, (x, log_q) is differentiable in the parameters -- the pass runs through the
+        layers' autograd nodes, the noise carries no gradient -- which makes the reverse-KL objective
+        ``(log_q - log_p_target(x)).mean()`` a function of the seeded stream.  Without the flag a seeded call runs under
+        ``no_grad`` as before."""
         if seed is None:
             if first_row != 0:
                 raise ValueError("first_row names a row of the seeded stream: pass seed= as well")
             z = self.base.sample(*num_samples)
-            xs, _ = self.forward(z)
-            return xs[-1]
+            if not return_log_prob:
+                xs, _ = self.forward(z)
+                return xs[-1]
+            if z.dim() == 2 and z.shape[0] == 0:
+                return z, z.new_empty(0)
+            xs, log_det = self._pass(z, False, last_only=True)
+            return xs[-1], self.base.log_prob(z) - log_det
         if not isinstance(self.base, StandardNormal):
             raise ValueError("seeded sampling needs a StandardNormal base: the stream is defined for N(0, I)")
         if len(num_samples) != 1 or isinstance(num_samples[0], bool) or not isinstance(num_samples[0], int) or num_samples[0] < 0:
@@ -3170,6 +3223,8 @@ class NormalizingFlowModel(NormalizingFlow):
         if isinstance(first_row, bool) or not isinstance(first_row, int) or first_row < 0:
             raise ValueError("first_row must be a non-negative integer")
         n, seed = num_samples[0], int(seed) & 0xFFFFFFFFFFFFFFFF
+        if return_log_prob:
+            return self._sample_log_q(n, seed, first_row)
         with torch.no_grad():
             run = self._sample_run()
             if run is not None and n > 0:
@@ -3182,6 +3237,37 @@ class NormalizingFlowModel(NormalizingFlow):
             z = self.base.sample((n,), seed=seed, first_row=first_row)
             xs, _ = self._pass(z, False, last_only=True)  # (no intermediates where a run is fused)
             return xs[-1]
+
+    def _sample_log_q(self, n: int, seed: int, first_row: int) -> tuple[Tensor, Tensor]:
+        """``sample(n, seed=, first_row=, return_log_prob=True)`` after its argument checks.  The route is that of the
+        seeded sample -- it depends on the model and the device, not on the row count -- except that a call that wants
+        gradients takes the general route whatever the model (the one-launch route has no gradient kernel)."""
+        dim = self.base.dim
+        if n == 0:
+            return (torch.empty((0, dim), dtype=torch.float32, device=self.base.device),
+                    torch.empty(0, dtype=torch.float32, device=self.base.device))
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            with torch.no_grad():
+                z, sq = self.base._sample_sq(n, seed, first_row)
+            xs, log_det = self._pass(z, False, last_only=True)  # the layers' autograd nodes
+            return xs[-1], (-0.5 * sq - 0.5 * dim * math.log(2 * math.pi)) - log_det
+        with torch.no_grad():
+            run = self._sample_run()
+            if run is not None:
+                dev = self.base.device  # (as sample(seed=): "cuda" -> the current device, one image cache)
+                if dev.type == "cuda" and dev.index is None:
+                    dev = torch.device("cuda", torch.cuda.current_device())
+                res = run.launch_sample_logq(seed, first_row, n, dev, run.ready_for(n, dev))
+                if res is not None:
+                    return res
+            z, sq = self.base._sample_sq(n, seed, first_row)
+            xs, log_det = self._pass(z, False, last_only=True)  # (the forward log_det; no intermediates where a run is fused)
+            log_det = log_det.to(torch.float32).contiguous()
+            log_q = torch.empty_like(log_det)
+            with torch.cuda.device(log_q.device):
+                _lib.check("mnf_gauss_logq_sq", _lib.load().mnf_gauss_logq_sq(
+                    sq.data_ptr(), log_det.data_ptr(), log_q.data_ptr(), n, dim, _stream()))
+            return xs[-1], log_q
 
     def _sample_run(self) -> "_AffineRun | None":
         """The model as ONE run of AffineHalfFlow layers (a single layer included: ``_affine_runs`` starts at two), or
