@@ -65,7 +65,7 @@ extern "C" {
 
 /* Bumped whenever an entry point's signature or meaning changes; mnf_abi_version() returns the value the
  * library was built with, so a binding can refuse a stale build. */
-#define MNF_ABI_VERSION 31
+#define MNF_ABI_VERSION 32
 int mnf_abi_version(void);
 const char* mnf_error_string(int code);
 /* hipError_t of the last failed launch on the calling thread (0 if none). */
@@ -208,6 +208,34 @@ int mnf_affine_half_rt_stack(const float* x, float* y, float* intermediates, flo
  * weights there; one launch for the run measured 4 % slower than one per layer). */
 int mnf_affine_half_rt_stack_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
                                        int n_layers);
+/* Seeded sampling as ONE launch of the run-time-shaped kernel (kernel family "ahf_stack_rt_sample", "ahf_rt_sample" for
+ * one layer): mnf_affine_half_stack_sample for the shapes without a split stack kernel.  The first layer's rows are not
+ * read but generated in registers, z[r][c] = the counter-based N(0, 1) of (seed, row0 + r, c) that mnf_normal_rows(seed,
+ * row0, ., rows, dim) writes (bit for bit, odd halves included); the layers after the first run in place in y, which is the
+ * only tensor the launch writes.  y equals mnf_affine_half_rt_stack(forward, intermediates = NULL) on the materialised
+ * noise, bit for bit, and is a pure function of (seed, row0 + r, parameters).  flats / parity_host / has_scale /
+ * has_shift as mnf_affine_half_rt_stack.
+ * MNF_ERR_INVALID_ARG before any launch: NULL y / flats / parity_host, a pointer that is not 4-byte aligned, n_layers
+ * outside 1 .. 32, rows < 0, row0 < 0, odd dim or dim < 2, a bad hidden list, neither scale nor shift.  rows == 0: MNF_OK,
+ * nothing is touched.  MNF_ERR_UNSUPPORTED where mnf_affine_half_rt_stack_sample_supported() is 0 (caller:
+ * mnf_normal_rows, then mnf_affine_half_rt_stack).  A y that is only 4-byte aligned takes the kernels without vector row
+ * accesses, as the forward entry does.  Never allocates or synchronises; capturable. */
+int mnf_affine_half_rt_stack_sample(uint64_t seed, int64_t row0, float* y, const float* flats, const int* parity_host,
+                                    int n_layers, int64_t rows, int dim, int n_hidden, const int* hidden_host,
+                                    int has_scale, int has_shift, void* stream);
+/* mnf_affine_half_rt_stack_sample that also writes the sample's own log-density (kernel family
+ * "ahf_stack_rt_sample_lq", "ahf_rt_sample_lq" for one layer): log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r), as
+ * mnf_affine_half_stack_sample_logq defines it, 4 more bytes per row.  y is bit for bit mnf_affine_half_rt_stack_sample's;
+ * log_q[r] is a pure function of (seed, row0 + r, parameters) (mnf_ahf_rt.hip's header comment gives the fp32 order of
+ * the sum).  Argument checks as mnf_affine_half_rt_stack_sample, plus MNF_ERR_INVALID_ARG for a NULL log_q or one that is
+ * not 4-byte aligned. */
+int mnf_affine_half_rt_stack_sample_logq(uint64_t seed, int64_t row0, float* y, float* log_q, const float* flats,
+                                         const int* parity_host, int n_layers, int64_t rows, int dim, int n_hidden,
+                                         const int* hidden_host, int has_scale, int has_shift, void* stream);
+/* Host-side query of the shape alone (no device needed): mnf_affine_half_rt_stack_supported's answer for the same
+ * arguments -- every plan of the run-time-shaped kernel has a sampling instantiation, which serves both entries. */
+int mnf_affine_half_rt_stack_sample_supported(int dim, int n_hidden, const int* hidden_host, int has_scale, int has_shift,
+                                              int n_layers);
 /* Split image of one layer: n_split_words 32-bit words of packed f16 (hi | scaled lo) operands, then
  * n_plain_words fp32 words (biases), then MNF_SPLIT_TAIL_WORDS words written by the pack call (word 0
  * = bit pattern of max |weight|: the kernels take the fp32 path when it leaves the f16 range).

@@ -64,8 +64,10 @@ MNF_NO_RUN_FUSION and MNF_NO_PAIR_FUSION (layer-by-layer passes, for per-layer m
 |                          | else            | anything (element by element)                     | nsf_ar_generic (VALU)          |
 | NSF_AR.forward bwd       | any             | anything (element by element)                     | nsf_ar_bwd_generic (VALU, atomics) |
 | NormalizingFlowModel.sample(seed=) | any    | the model is ONE run of AffineHalfFlow layers on ahf_split_stack's full-tile shapes (d / 2 in 16/32/64/128) | ahf_split_stack_sample (one launch, noise in-kernel) |
+|                          | >= RT_SAMPLE_MIN_ROWS (opt-in: None) | the model is ONE run of AffineHalfFlow layers on ahf_rt / ahf_stack_rt (no gradients wanted) | ahf_rt_sample / ahf_stack_rt_sample (one launch, noise in-kernel) |
 |                          | else            | anything (StandardNormal base)                    | mnf_normal_rows' noise launch, then forward's rows above without intermediates |
 | sample(seed=, return_log_prob=True) | any   | as the one-launch row above, no gradients wanted  | ahf_split_stack_sample_lq (one launch: x and log_q) |
+|                          | >= RT_SAMPLE_MIN_ROWS (opt-in: None) | as the ahf_stack_rt_sample row above, no gradients wanted | ahf_rt_sample_lq / ahf_stack_rt_sample_lq (one launch: x and log_q) |
 |                          | else            | anything (StandardNormal base); any model when gradients are wanted | mnf_normal_rows_sq (noise + |z|^2), forward's rows above without intermediates, mnf_gauss_logq_sq |
 | MNFConv2d.forward        | MNF_CONV_FUSED (opt-in: False) | n_out <= 64, n_in k^2 <= 4096          | mnf_conv_fwd (one launch behind the operands) |
 |                          | else            | anything                                          | MIOpen convolutions between the library's operand and noise launches |
@@ -101,6 +103,11 @@ mnf_affine_half_stack_sample_logq_supported() (the same shapes); log_q[r] = log 
 the stack launch, or on the general row from |z|^2 (summed in the noise launch's registers) and forward's log_det.  A call
 with grad mode on and a parameter that requires grad takes the general row whatever the model: the pass then runs through
 the layers' autograd nodes (there is no gradient kernel for the one launch), with gauss_logq_sq's formula as tensor ops.
+
+The RT_SAMPLE_MIN_ROWS rows are the same two calls for a model whose run is on the run-time-shaped tier (ready_for answers
+("rt", parameters): rt_route's conditions, so never below RT_MIN_ROWS unless every layer has force_generic = 2): from
+RT_SAMPLE_MIN_ROWS rows on the call is ONE mnf_affine_half_rt_stack_sample(_logq) launch, the first layer's rows generated in
+the kernel's registers, where mnf_affine_half_rt_stack_sample_supported() has the shape; x is bit for bit the general row's.
 
 Two requests override the shape: an fp32 request (layer.force_fp32_mfma / MNF_FP32_MFMA=1) never lands on the *_rt
 kernels, whose arithmetic is split-f16 -- it takes the fp32 matrix-core kernel where the shape has one (AffineHalfFlow and
@@ -290,6 +297,23 @@ MNF_CONV_FUSED = False
 # switch has no threshold to offer yet.
 MNF_CONV_BWD_FUSED = False
 
+# Seeded sampling of a model that is one run of AffineHalfFlow layers on the run-time-shaped tier (ahf_rt / ahf_stack_rt) as
+# ONE launch whose first layer generates its rows (csrc/mnf_ahf_rt.hip ahf_rt_sample_kernel; flows._AffineRun._launch_sample_rt,
+# DESIGN.md 3.8p), with log_q from the same launch under return_log_prob=True: from this many rows on, None = never (the
+# general route: mnf_normal_rows(_sq), ahf_stack_rt, mnf_gauss_logq_sq).  Read at every call; never effective below what
+# _AffineRun.rt_route accepts (RT_MIN_ROWS, or any row count when every layer has force_generic = 2).
+# Measured (tools/time_sample_rt.py, profiles/r31/sample_rt_ab.txt: microseconds per call, median of 15, every column a fresh
+# process, general / one launch / general / one launch): the one launch wins 20 of 24 cells and is level in one, by most
+# where the call is launch-bound -- (6, (8,)) x 3 at 4,096 rows 88 -> 53 (0.60 x), (64, (24, 24)) x 3 at 4,096 rows 107 -> 69
+# (0.65 x), at 2^16 138 -> 99, at 2^18 244 -> 227 (0.93 x), at 2^20 835 -> 699; x 9 layers at 4,096 rows 206 -> 157, at 2^16
+# 285 -> 240, at 2^18 605 -> 598 (level), at 2^20 2,095 -> 1,964 -- and LOSES three cells at the largest sizes: (64, (24, 24))
+# x 9 at 2^20 rows with log_q 2,040 -> 2,113 (1.036 x), c6's model (dim 512, 9 layers) at 2^18 rows 2,820 -> 2,880 x only
+# (1.021 x) and 2,678 -> 2,924 with log_q (1.092 x); at 2^16 rows c6 wins (836 -> 793, 809 -> 775).  There the in-register
+# Box-Muller of layer 0 (one or two waves per SIMD at 226-256 registers) costs more than the noise tensor's round trip
+# saves, and the general route's mnf_normal_rows_sq is the faster materialiser.  The lost cells are at the top of the row
+# range, so no row count exists from which every cell is won or level: the switch ships None.
+RT_SAMPLE_MIN_ROWS = None
+
 NO_FUSED_LOGPROB = False  # measurements: the log-prob epilogue stays its own launch after an affine run
 
 
@@ -432,4 +456,4 @@ def tier(kind: str, direction: str, rows: int, dim: int, hidden, K: int | None =
 
 def tier_of_kernel(name: str) -> str:
     """The tier a kernel family name (torch_mnf_amd.last_kernel()) belongs to."""
-    return "valu" if "generic" in name else "rt" if name.endswith("_rt") else "per-shape"
+    return "valu" if "generic" in name else "rt" if name.endswith("_rt") or "_rt_sample" in name else "per-shape"

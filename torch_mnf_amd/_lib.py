@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MNF_LIB_PATH") or os.path.join(_HERE, "libmnf_hip.so")  # override: A/B builds
 
-ABI_VERSION = 31  # include/mnf_hip.h MNF_ABI_VERSION
+ABI_VERSION = 32  # include/mnf_hip.h MNF_ABI_VERSION
 MNF_OK = 0
 MNF_ERR_INVALID_ARG = -1
 MNF_ERR_UNSUPPORTED = -2
@@ -142,6 +142,11 @@ SIGNATURES = {
     "mnf_affine_half_rt_stack_supported": (c_int, [c_int, c_int, _intp, c_int, c_int, c_int]),
     "mnf_affine_half_rt_stack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                          _intp, c_int, c_int64, c_int, c_int, c_int, _intp, c_int, c_int, c_void_p]),
+    "mnf_affine_half_rt_stack_sample": (c_int, [c_uint64, c_int64, c_void_p, c_void_p, _intp, c_int, c_int64, c_int, c_int,
+                                                _intp, c_int, c_int, c_void_p]),
+    "mnf_affine_half_rt_stack_sample_logq": (c_int, [c_uint64, c_int64, c_void_p, c_void_p, c_void_p, _intp, c_int, c_int64,
+                                                     c_int, c_int, _intp, c_int, c_int, c_void_p]),
+    "mnf_affine_half_rt_stack_sample_supported": (c_int, [c_int, c_int, _intp, c_int, c_int, c_int]),
     "mnf_affine_half_bwd_rt_supported": (c_int, [c_int, c_int, _intp, c_int, c_int]),
     "mnf_affine_half_bwd_rt_stack_supported": (c_int, [c_int, c_int, _intp, c_int, c_int, c_int]),
     "mnf_affine_half_bwd_rt_stack": (c_int, [c_void_p] * 10 + [_intp, c_int, c_int64, c_int, c_int, c_int, _intp, c_int, c_int,

@@ -2347,6 +2347,7 @@ class _AffineRun:
         self._rt_bwd_wide_ok = None  # mnf_affine_half_bwd_rt_wide_stack_supported, asked once
         self._sample_ok = None    # mnf_affine_half_stack_sample_supported, asked once
         self._sample_lq_ok = None  # mnf_affine_half_stack_sample_logq_supported, asked once
+        self._rt_sample_ok = None  # mnf_affine_half_rt_stack_sample_supported, asked once
         self._rt_now = False      # the call in flight trains on the run-time-shaped route (launch_grad -> _AffineRunFn)
         # the owner's switch (NormalizingFlow / FusedAffineStack .fuse_rt_training), copied here before every pass
         self.fuse_rt_training = False
@@ -2506,13 +2507,49 @@ class _AffineRun:
             return ("rt", self.rt_flat(device))
         return None
 
+    def _launch_sample_rt(self, seed: int, first_row: int, rows: int, device, flat: Tensor, with_logq: bool):
+        """The seeded rows as ONE launch of the run-time-shaped kernel (``mnf_affine_half_rt_stack_sample``, or ``_logq``:
+        kernel families ``ahf_stack_rt_sample(_lq)``, ``ahf_rt_sample(_lq)`` for one layer): the first layer's rows are
+        generated in registers, the later layers run in place in x.  ``flat``: ``ready_for``'s parameters.  None below
+        ``_dispatch.RT_SAMPLE_MIN_ROWS`` (None: never) or where the library has no such launch for the shape."""
+        floor = _dispatch.RT_SAMPLE_MIN_ROWS
+        if floor is None or rows < floor or self._rt_sample_ok is False:
+            return None
+        f0, n = self.layers[0], len(self.layers)
+        lib = _lib.load()
+        shape = (len(f0.h_sizes), f0._hid, int(f0.scale), int(f0.shift))
+        if self._rt_sample_ok is None:
+            self._rt_sample_ok = bool(lib.mnf_affine_half_rt_stack_sample_supported(f0.dim, *shape, n))
+            if not self._rt_sample_ok:
+                return None
+        y = torch.empty((rows, f0.dim), dtype=torch.float32, device=device)
+        log_q = torch.empty(rows, dtype=torch.float32, device=device) if with_logq else None
+        par = _lib.int_array([int(bool(f.parity)) for f in self.layers])
+        with torch.cuda.device(y.device):
+            if with_logq:
+                name = "mnf_affine_half_rt_stack_sample_logq"
+                rc = lib.mnf_affine_half_rt_stack_sample_logq(ctypes.c_uint64(seed), first_row, y.data_ptr(), log_q.data_ptr(),
+                                                              flat.data_ptr(), par, n, rows, f0.dim, *shape, _stream())
+            else:
+                name = "mnf_affine_half_rt_stack_sample"
+                rc = lib.mnf_affine_half_rt_stack_sample(ctypes.c_uint64(seed), first_row, y.data_ptr(), flat.data_ptr(), par, n,
+                                                         rows, f0.dim, *shape, _stream())
+        if rc == _lib.MNF_ERR_UNSUPPORTED:
+            self._rt_sample_ok = False
+            return None
+        _lib.check(name, rc)
+        return (y, log_q) if with_logq else y
+
     def launch_sample(self, seed: int, first_row: int, rows: int, device, images: tuple | None) -> Tensor | None:
         """Rows ``first_row .. first_row + rows - 1`` of the seeded sample as ONE ``mnf_affine_half_stack_sample``
         launch: the noise z[r, c] = z0_normal(seed, r, c) is generated in the stack kernel's registers, the layers are
         applied in model order and only x is written.  ``images``: from ``ready_for``.  None when the run is not on
         the split per-shape route or the library has no sample launch for the shape (the caller then materialises
-        the noise and runs the ordinary pass)."""
+        the noise and runs the ordinary pass).  A run on the run-time-shaped route (``images`` = ("rt", parameters)) takes
+        ``_launch_sample_rt``."""
         f0, n = self.layers[0], len(self.layers)
+        if images is not None and isinstance(images[0], str):
+            return self._launch_sample_rt(seed, first_row, rows, device, images[1], False)
         if images is None or isinstance(images[0], str) or images[1] is None or self._sample_ok is False:
             return None
         if self._sample_ok is None:
@@ -2537,6 +2574,8 @@ class _AffineRun:
         launch writes x and log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r) (4 more bytes per row).  None under
         ``launch_sample``'s conditions, by this entry's own shape query (the caller then takes the general route)."""
         f0, n = self.layers[0], len(self.layers)
+        if images is not None and isinstance(images[0], str):
+            return self._launch_sample_rt(seed, first_row, rows, device, images[1], True)
         if images is None or isinstance(images[0], str) or images[1] is None or self._sample_lq_ok is False:
             return None
         if self._sample_lq_ok is None:
@@ -3192,15 +3231,17 @@ class NormalizingFlowModel(NormalizingFlow):
         (``mnf_normal_rows`` materialises it, tests/rng_reference.py restates it on the host).  A pure function of
         (seed, row, parameters): chunks and per-rank row ranges of one seed concatenate to the whole.  A model that is
         one run of AffineHalfFlow layers on the split per-shape stack kernel draws the noise inside that kernel -- ONE
-        launch that reads no row tensor and writes only x (``ahf_split_stack_sample``); every other model materialises
-        the noise and runs the pass without intermediates.  Both routes compute the same sample.
+        launch that reads no row tensor and writes only x (``ahf_split_stack_sample``); a run on the run-time-shaped
+        kernel does the same from ``_dispatch.RT_SAMPLE_MIN_ROWS`` rows on (``ahf_stack_rt_sample``, one layer:
+        ``ahf_rt_sample``); every other model materialises the noise and runs the pass without intermediates.  All routes
+        compute the same sample.
 
         ``return_log_prob=True`` returns ``(x, log_q)``: log_q (n,) fp32 is the model's density at its own sample,
         log_q[r] = log N(z_r; 0, I) - log_det_forward(z_r) -- mathematically ``log_prob(x)[r]``, from the ONE forward pass
         that produced x (``log_prob(x)`` runs every layer again, in the inverse direction).  x is the x of the same call
         without the flag.  With ``seed`` log_q is a pure function of (seed, row, parameters) as x is, so pieces
-        concatenate; the one-launch models write it from the same launch (``ahf_split_stack_sample_lq``), every other
-        model takes ``mnf_normal_rows_sq`` (noise and its |z|^2), the pass, and ``mnf_gauss_logq_sq``.  When grad mode is
+        concatenate; the one-launch models write it from the same launch (``ahf_split_stack_sample_lq``;
+        ``ahf_stack_rt_sample_lq`` / ``ahf_rt_sample_lq`` on the run-time-shaped route), every other model takes ``mnf_normal_rows_sq`` (noise and its |z|^2), the pass, and ``mnf_gauss_logq_sq``.  When grad mode is
         on and a parameter requires grad, (x, log_q) is differentiable in the parameters -- the pass runs through the
         layers' autograd nodes, the noise carries no gradient -- which makes the reverse-KL objective
         ``(log_q - log_p_target(x)).mean()`` a function of the seeded stream.  Without the flag a seeded call runs under
